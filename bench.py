@@ -16,6 +16,8 @@ writes every amplitude once = 32 B x 2^n; per-gate kernels use the per-gate byte
 by its HIP-event-timed average duration inside the timed region (events on the last tenth of the
 timed steps, at least one: at 20 qubits events on every launch would add ~35 % to the step), against
 8 TB/s.
+A plain run sets up, warms up, times --steps steps and prints the line; --dump-outputs DIR adds
+the last timed step's outputs as DIR/<name>.npy.  What follows is measured only with --full.
 roofline_1q28 / roofline_batch16: north_star's single-qubit target (W-1Q, 28 qubits) and BASELINE
 config 4 (W-BATCH 16q x 1024 under the reference noise process, the BatchedSimulator default, and
 under the physical process) measured in the same run.
@@ -125,7 +127,17 @@ def parse():
                    help="bracket that timed region (only) with roctxProfilerResume / Pause, for "
                         "rocprofv3 --selected-regions: the profile then holds exactly the launches "
                         "the line's roofline averages (scripts/roofline_check.py recomputes it)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline figure: the extra objects "
+                        "(--extras), roofline_1q28, roofline_batch16 and cpu_baseline (--cpu-budget). "
+                        "Without it a run sets up, warms up, times --steps steps and prints the line")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last one left (the state's amplitudes, "
+                        "W-BATCH: the average probabilities) to DIR/<name>.npy, float64 (one GPU)")
     a = p.parse_args()
+    if not a.full:
+        a.no_extras = a.no_1q28 = a.no_batch16 = True
+        a.cpu_budget = 0.0
     PROFILE_REGION[0] = a.profile_region
     if a.qubits is None:
         a.qubits = {"batch": 16, "dm": 14, "noisy": 26}.get(a.workload, 30)
@@ -158,6 +170,47 @@ def alg_bytes_of_circuit(circuit, n):
         else:  # CZ, Toffoli
             total += 8 * N
     return total
+
+
+DUMP_RUN_AMPS = 1024  # amplitudes per sampled run (16 KiB)
+DUMP_RUNS = 1024      # sampled runs of a state too large to dump whole: 16 MiB of amplitudes
+
+
+def dump_array(dump_dir, name, a):
+    import numpy as np
+    os.makedirs(dump_dir, exist_ok=True)
+    np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
+def dump_state(sv, dump_dir, name, seed):
+    """--dump-outputs: the amplitudes of StateVector `sv` as a caller reads them (toHost /
+    getStateVector: the identity layout) in DIR/<name>.npy, float64 of shape (K, 2) = (re, im).
+    A state of at most DUMP_RUNS x DUMP_RUN_AMPS amplitudes is written whole.  Of a larger one
+    (30 qubits are 16 GiB) a fixed sample: DUMP_RUNS runs of DUMP_RUN_AMPS consecutive amplitudes,
+    their starts drawn once from numpy's default_rng(seed) — the same indices in every run with the
+    same arguments — each copied from the device on its own; DIR/<name>_index.npy holds the
+    indices (float64: exact below 2^53)."""
+    import ctypes
+    import numpy as np
+    from qsim_amd import _lib
+    size = sv.getSize()
+    if size <= DUMP_RUNS * DUMP_RUN_AMPS:
+        dump_array(dump_dir, name, sv.toHost().view(np.float64).reshape(-1, 2))
+        return
+    rng = np.random.default_rng(seed)
+    starts = np.sort(rng.choice(size // DUMP_RUN_AMPS, DUMP_RUNS, replace=False)) * DUMP_RUN_AMPS
+    base = sv.devicePtr()  # (restores the identity layout first)
+    sv.synchronize()
+    copy = _lib.hip.hipMemcpy  # the HIP runtime the engine links
+    copy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+    copy.restype = ctypes.c_int
+    out = np.empty((DUMP_RUNS, DUMP_RUN_AMPS), dtype=np.complex128)
+    for i, s0 in enumerate(starts):
+        rc = copy(out[i].ctypes.data, base + 16 * int(s0), 16 * DUMP_RUN_AMPS, 2)  # 2: device to host
+        if rc != 0:
+            raise RuntimeError(f"hipMemcpy of amplitudes [{s0}, {s0 + DUMP_RUN_AMPS}) failed: error {rc}")
+    dump_array(dump_dir, name, out.view(np.float64).reshape(-1, 2))
+    dump_array(dump_dir, name + "_index", (starts[:, None] + np.arange(DUMP_RUN_AMPS)[None, :]).reshape(-1))
 
 
 def cpu_baseline(circuit, n, budget, q=None, args=None):
@@ -494,6 +547,8 @@ def run_single(args):
         "effective_GBps": round(eff, 1),
         "kernels": stats,
     }
+    if args.dump_outputs:
+        dump_state(sim.state, args.dump_outputs, "state_vector", args.seed)
     del sim
     ex = set() if args.no_extras else set(args.extras.split(","))
     if args.workload == "hc":
@@ -700,7 +755,7 @@ def _dominant_roofline(stats):
             "avg_launch_ms": round(avg_s * 1e3, 4), "launches": dom["launches"]}
 
 
-def measure_dm(q, n, steps, warmup, jit, seed, depth, p_noise):
+def measure_dm(q, n, steps, warmup, jit, seed, depth, p_noise, dump=None):
     """DensityMatrixSimulator (src/DensityMatrix.cu:978-1122): rho of n qubits as a 2n-index-bit
     engine state (4^n x 16 B), the W-HC circuit with depolarizing p on all qubits (the reference
     applies each channel after a gate that touches its qubit).  gates/s = circuit gates / median
@@ -731,6 +786,8 @@ def measure_dm(q, n, steps, warmup, jit, seed, depth, p_noise):
     sv.profile(False)
     passes, jit_passes = sv.lastRunInfo()
     tr = sim.getTrace()
+    if dump:
+        dump_state(sv, dump, "density_matrix", seed)
     del sim
     med = _median(ts)
     return {"workload": f"DensityMatrixSimulator {n} qubits (rho: {2 * n} index bits, {16 << (2 * n)} B), "
@@ -740,7 +797,7 @@ def measure_dm(q, n, steps, warmup, jit, seed, depth, p_noise):
             "kernels": stats}
 
 
-def measure_noisy(q, n, steps, warmup, seed, depth, p_noise):
+def measure_noisy(q, n, steps, warmup, seed, depth, p_noise, dump=None):
     """NoisySimulator (src/NoiseModel.cu:117-314): the W-HC circuit with depolarizing p on all n
     qubits, every channel entry a per-pair Monte-Carlo pass after every gate (the reference's
     structure; flips walked geometrically, noise.hip).  gates/s = circuit gates / median run."""
@@ -764,6 +821,10 @@ def measure_noisy(q, n, steps, warmup, seed, depth, p_noise):
         sim.synchronize()
         ts.append(time.perf_counter() - t0)
     stats = sv.profileStats()
+    if dump:  # (the last timed run's state, before the untimed run below)
+        sv.profile(False)
+        dump_state(sv, dump, "state_vector", seed)
+        sv.profile(True)
     # The pulled path builds the next step's code words (noise_map) on a second stream beside the
     # pull pass, so their HIP-event spans overlap and each includes time shared with the other
     # kernel.  One more run with the map on the main stream (QSIM_NOISE_MAP_OVERLAP=0, same states)
@@ -852,7 +913,7 @@ def roofline_1q28(q, steps=3):
             "gates_per_s": round(100 * steps / wall, 1), "target_frac": 0.70}
 
 
-def measure_batch(q, n, B, steps, warmup, jit, seed, depth, p_noise, process, pmc_path=None):
+def measure_batch(q, n, B, steps, warmup, jit, seed, depth, p_noise, process, pmc_path=None, dump=None):
     """W-BATCH (BASELINE config 4): BatchedSimulator, n qubits x B trajectories, depolarizing p on
     every qubit after every gate (NoiseModel.addDepolarizingAll), the W-HC circuit, under one noise
     process.  Returns value (trajectory-gates/s), ms per step, the kernel table and the dominant
@@ -878,6 +939,10 @@ def measure_batch(q, n, B, steps, warmup, jit, seed, depth, p_noise, process, pm
         sim.synchronize()
     wall = time.perf_counter() - t0
     stats = sim.profileStats()
+    if dump:  # (the last timed step's ensemble, before the untimed steps below)
+        sim.profile(False)
+        dump_array(dump, "average_probabilities", sim.getAverageProbabilities())
+        sim.profile(True)
     overlapped = None
     if split:
         # The timed steps overlap the two halves' kernels (each launch's HIP-event span includes
@@ -969,7 +1034,8 @@ def run_batch(args):
     import qsim_amd as q
     n, B = args.qubits, args.trajectories
     m = measure_batch(q, n, B, args.steps, args.warmup, args.jit, args.seed, args.depth, args.noise,
-                      args.batch_noise, args.pmc_json or batch_pmc_path(n, args.batch_noise))
+                      args.batch_noise, args.pmc_json or batch_pmc_path(n, args.batch_noise),
+                      args.dump_outputs)
     out = {
         "metric": "trajectory-gates/s, W-HC circuit on noisy trajectories (BatchedSimulator)",
         "value": m["value"], "unit": "trajectory-gates/s",
@@ -991,10 +1057,12 @@ def run_model_line(args):
     """--workload dm / noisy: one line for the §8(f) simulators (value = circuit gates/s)."""
     import qsim_amd as q
     if args.workload == "dm":
-        m = measure_dm(q, args.qubits, args.steps, args.warmup, args.jit, args.seed, args.depth, args.noise)
+        m = measure_dm(q, args.qubits, args.steps, args.warmup, args.jit, args.seed, args.depth, args.noise,
+                       args.dump_outputs)
         metric = "gates/s, W-HC circuit with depolarizing noise (DensityMatrixSimulator)"
     else:
-        m = measure_noisy(q, args.qubits, args.steps, args.warmup, args.seed, args.depth, args.noise)
+        m = measure_noisy(q, args.qubits, args.steps, args.warmup, args.seed, args.depth, args.noise,
+                          args.dump_outputs)
         metric = "gates/s, W-HC circuit with depolarizing noise (NoisySimulator)"
     out = {"metric": metric, "value": m["value"], "unit": "gates/s", "n_gpus": 1, "steps": args.steps,
            "warmup": args.warmup, "ms_per_step": m["ms_per_step"], "higher_is_better": True,
@@ -1007,6 +1075,8 @@ def run_model_line(args):
 
 def main():
     args = parse()
+    if args.dump_outputs and (args.gpus > 1 or args.dry_run or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        sys.exit("--dump-outputs writes the outputs of a one-GPU run (--gpus 1, no --dry-run)")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # No launcher around us: start the N rank processes ourselves and relay rank 0's JSON
         # line (qsim_amd/launch.py).  launch.py is loaded by file path, not through the package:

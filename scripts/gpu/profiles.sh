@@ -15,7 +15,7 @@ mkdir -p $O
 prof() {  # region, extra bench args...
   local rg=$1; shift
   cd /tmp && timeout -k 10 400 rocprofv3 --marker-trace --kernel-trace --stats --output-format csv \
-    -d $O/prof_$rg -o $rg -- python3 $R/bench.py --cpu-budget 0 --profile-region $rg "$@" \
+    -d $O/prof_$rg -o $rg -- python3 $R/bench.py --full --cpu-budget 0 --profile-region $rg "$@" \
     > $O/bench_$rg.json 2> $O/bench_$rg.err || { tail -5 $O/bench_$rg.err; return 1; }
   cd $R
   python3 scripts/roofline_check.py $rg $O/bench_$rg.json $O/prof_$rg/${rg}_kernel_trace.csv $O/check_$rg.json \

@@ -11,7 +11,7 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 600 --timeout
 tail -3 $O/pytest_gpu.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-timeout -k 10 600 python -u bench.py --steps 20 --warmup 2 > $O/bench.json 2> $O/bench.err || { tail -10 $O/bench.err; exit 1; }
+timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 2 > $O/bench.json 2> $O/bench.err || { tail -10 $O/bench.err; exit 1; }
 python3 - $O/bench.json <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -6,7 +6,8 @@
 
 <region> is one of bench.py's --profile-region names.  The trace comes from
     rocprofv3 --selected-regions --kernel-trace --stats --output-format csv -- \
-        python3 bench.py --profile-region <region> ...
+        python3 bench.py --full --profile-region <region> ...
+(--full: the W-HC line's objects other than its headline are measured only by a full run)
 so it holds only the launches of that timed region (roctxProfilerResume / Pause around it).  The
 line's roofline for the region (achieved = algorithmic bytes per launch / average launch time from
 HIP events on the engine's stream) is recomputed from the rocprof durations of the same kernels:

@@ -29,7 +29,7 @@ def _env():
 @pytest.mark.parametrize("world", [2, 4])
 def test_dry_run_launch_prints_one_json_line(world):
     r = subprocess.run([sys.executable, BENCH, "--gpus", str(world), "--dry-run", "--steps", "2",
-                        "--warmup", "1", "--qubits", "24", "--cpu-budget", "1"], capture_output=True,
+                        "--warmup", "1", "--qubits", "24", "--full", "--cpu-budget", "1"], capture_output=True,
                        text=True, timeout=300, env=_env())
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -132,7 +132,7 @@ def test_batch_dry_run_shards_trajectories(world, total):
     ranks' averages is a probability vector, one JSON line."""
     r = subprocess.run([sys.executable, BENCH, "--workload", "batch", "--gpus", str(world), "--dry-run",
                         "--steps", "2", "--warmup", "1", "--qubits", "10", "--trajectories", str(total),
-                        "--cpu-budget", "1"],
+                        "--full", "--cpu-budget", "1"],
                        capture_output=True, text=True, timeout=300, env=_env())
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]

@@ -248,6 +248,7 @@ struct qsim_batch {
     size_t frames_cap = 0;
     DevBuf ops, stages;             // fused-plan descriptors
     DevBuf cliff;                   // per-step Clifford codes of the current run (frame build)
+    DevBuf expect_terms;            // term table of the last expectation value (expect.hip)
     PlanCache plans;
     Timer timer;
     Scratch scratch, scratch2;
@@ -942,6 +943,24 @@ int qsim_batch_traj_state(qsim_batch* b, int traj, double* dst) {
     });
 }
 
+// Reads b->d under b->perm: carried frames are applied (materialize), the layout is not restored.
+int qsim_batch_expectation(qsim_batch* b, const qsim_pauli_term* terms, size_t count, double* per_traj) {
+    return bguard([&] {
+        need(b);
+        if (!per_traj || (count && !terms)) fail(QSIM_ERR_INVALID_ARGUMENT, "null buffer");
+        const ExpectPlan plan = lower_expectation(b->n, terms, count, b->perm.empty() ? nullptr : b->perm.data());
+        const uint64_t B = (uint64_t)b->batch;
+        std::fill(per_traj, per_traj + B, 0.0);
+        if (plan.terms.empty()) return;
+        materialize(b);
+        // scratch = [per-trajectory sums B][partials B x chunks]
+        double* d_out = (double*)b->scratch.get((B + B * expect_chunks(B)) * sizeof(double), b->stream);
+        launch_expectation(b->d, b->n, B, plan, b->expect_terms, d_out + B, d_out, b->stream, &b->timer);
+        QSIM_HIPCHK(hipMemcpyAsync(per_traj, d_out, B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(b->stream));
+    });
+}
+
 int qsim_batch_device_ptr(qsim_batch* b, void** dptr) {
     return bguard([&] {
         need(b);
@@ -950,6 +969,14 @@ int qsim_batch_device_ptr(qsim_batch* b, void** dptr) {
         settle_in_d0(b);   // (pulled runs copy their result back to this buffer from now on)
         b->pinned = true;
         *dptr = b->d;
+    });
+}
+
+int qsim_batch_perm(qsim_batch* b, int32_t* perm) {
+    return bguard([&] {
+        need(b);
+        if (!perm) fail(QSIM_ERR_INVALID_ARGUMENT, "null perm");
+        for (int q = 0; q < b->n; ++q) perm[q] = b->perm.empty() ? q : b->perm[q];
     });
 }
 

@@ -186,6 +186,7 @@ struct qsim_state {
     double* d_partials = nullptr;
     double* d_result = nullptr;
     DevBuf ops, stages;  // fused-plan descriptors, re-uploaded only when the plan changes
+    DevBuf expect_terms;  // term table of the last expectation value (expect.hip)
     PlanCache plans;
     Timer timer;
     int last_passes = 0, last_jit_passes = 0;  // of the last fused run (qsim_state_last_run)
@@ -1477,6 +1478,34 @@ int qsim_state_prob_bit_zero(qsim_state* s, int bit, double* out) {
     });
 }
 
+// Reads s->d under s->perm as they are: no prep() / canonicalize(), nothing of the state changes.
+int qsim_state_expectation(qsim_state* s, const qsim_pauli_term* terms, size_t count, double* out) {
+    return guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        QSIM_REQUIRE(terms || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        const ExpectPlan plan = lower_expectation(s->n, terms, count, s->perm.empty() ? nullptr : s->perm.data());
+        *out = 0.0;
+        if (plan.terms.empty()) return;
+        DeviceGuard dg(s->device);
+        launch_expectation(s->d, s->n, 1, plan, s->expect_terms, s->d_partials, s->d_result, s->stream, &s->timer);
+        QSIM_HIPCHK(hipMemcpyAsync(out, s->d_result, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+    });
+}
+
+int qsim_expectation_plan(int n_qubits, const qsim_pauli_term* terms, size_t count, const int32_t* perm,
+                          int* passes, int* launches) {
+    return guarded([&] {
+        QSIM_REQUIRE(terms || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        QSIM_REQUIRE(passes && launches, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        const ExpectPlan plan = lower_expectation(n_qubits, terms, count, perm);
+        *passes = (int)plan.groups.size();
+        *launches = (int)plan.launches;
+    });
+}
+
 int qsim_state_max_abs_diff(qsim_state* a, qsim_state* b, double* out) {
     return guarded([&] {
         check_state(a);
@@ -1498,7 +1527,7 @@ int qsim_state_memory_bytes(qsim_state* s, uint64_t* bytes) {
         QSIM_REQUIRE(bytes, QSIM_ERR_INVALID_ARGUMENT, "null out");
         const uint64_t amps = sizeof(double2) << s->n;
         *bytes = amps + (s->alt_base ? amps : 0) + 4096 * sizeof(double) + sizeof(double) + s->scratch.cap +
-                 s->ops.cap + s->stages.cap + 2 * s->noise_codes_cap + 2 * s->noise_lists_cap;
+                 s->ops.cap + s->stages.cap + s->expect_terms.cap + 2 * s->noise_codes_cap + 2 * s->noise_lists_cap;
     });
 }
 

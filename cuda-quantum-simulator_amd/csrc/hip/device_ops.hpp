@@ -18,6 +18,14 @@ __device__ __forceinline__ double2 cadd(double2 a, double2 b) {
     return make_double2(a.x + b.x, a.y + b.y);
 }
 
+// Sum over the 64 lanes of a wave (the total lands in lane 0): the first stage of every
+// reduction (reduce.hip, expect.hip).
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    return v;
+}
+
 // Insert a zero bit at each of the `nfix` ascending positions `fix[]` of k.
 __device__ __forceinline__ uint64_t deposit(uint64_t k, int nfix, const int* fix) {
 #pragma unroll

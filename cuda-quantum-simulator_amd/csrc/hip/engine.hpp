@@ -447,6 +447,10 @@ void launch_probabilities(const double2* st, uint64_t count, double* out, hipStr
 // sum over |a_i|^2 for i with ((i >> bit) & 1) == 0 (bit < 0: all), deterministic 2-pass.
 double reduce_norm(const double2* st, int n, int bit, double* d_partials, double* d_result,
                    hipStream_t s);
+// Second stage of the reductions: result[r] (+)= the `count` partials of row r < rows, added in a
+// fixed order by one work-group per row (bitwise reproducible).
+void launch_sum_partials(const double* partials, int count, unsigned rows, double* result, bool accumulate,
+                         hipStream_t s);
 void launch_collapse(double2* st, int n, int bit, int result, double scale, hipStream_t s);
 // max over the 2^n amplitudes of the larger per-component |a - b| (d_partials: >= 2048 doubles).
 double reduce_max_abs_diff(const double2* a, const double2* b, int n, double* d_partials, double* d_result,
@@ -459,6 +463,35 @@ void sample_indices(const double2* st, int n, uint64_t batch, const double* unif
 // Average of |a|^2 over `batch` trajectories into out[2^n] (device).
 void launch_avg_probabilities(const double2* st, int n, uint64_t batch, double* out,
                               hipStream_t s);
+
+// Pauli-sum expectation values (expect.hip).  lower_expectation maps the terms' masks from logical
+// to physical bits through perm (null: identity), merges duplicate strings, drops zero
+// coefficients and groups the rest by physical x mask (one pass over the state per group; a
+// group of more than kExpectTerms terms takes several launches).  Throws Error on a mask bit >= n.
+constexpr int kExpectTerms = 256;  // capacity of a launch's term table in LDS
+struct ExpectTerm {
+    uint64_t z;     // physical z mask
+    double cr, ci;  // weights of Re a / Im a of a pair (x == 0: cr = c, the weight of |psi_i|^2)
+};
+struct ExpectGroup {
+    uint64_t x;  // physical x mask of every term in [begin, end)
+    size_t begin, end;
+};
+struct ExpectPlan {
+    std::vector<ExpectTerm> terms;
+    std::vector<ExpectGroup> groups;
+    size_t launches = 0;
+};
+ExpectPlan lower_expectation(int n, const qsim_pauli_term* terms, size_t count, const int* perm);
+size_t expect_chunks(uint64_t batch);  // partials per trajectory a launch may write
+// d_out[t] = the plan's sum on trajectory t of st ([batch][2^n]); terms: the owner's device copy of
+// the term table (uploaded here), d_partials: batch * expect_chunks(batch) doubles.  Nothing is
+// launched for an empty plan.  Asynchronous.
+struct DevBuf;
+void launch_expectation(const double2* st, int n, uint64_t batch, const ExpectPlan& plan, DevBuf& terms,
+                        double* d_partials, double* d_out, hipStream_t s, Timer* tm);
+// The z lane/run split of groups of at least kExpectSplitMin terms (QSIM_EXPECT_SPLIT, default 1).
+constexpr int kExpectSplitMin = 16;
 
 // ---------------------------------------------------------------------------------------
 // Timing (capi.hip): per-launch HIP events grouped by kernel name.

@@ -52,12 +52,6 @@ void launch_probabilities(const double2* st, uint64_t count, double* out, hipStr
     QSIM_HIPCHK(hipGetLastError());
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-    return v;
-}
-
 // Sum |a_i|^2 over the indices enumerated by k in [0, count): i = insert0(k, bit) if bit >= 0
 // (only bit==0 amplitudes; for bit >= 6 this halves the bytes read), else i = k.
 __global__ __launch_bounds__(256) void k_norm_partial(const double2* st, uint64_t count, int bit,
@@ -80,15 +74,26 @@ __global__ __launch_bounds__(256) void k_norm_partial(const double2* st, uint64_
     if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
+// result[r] (+)= the `count` partials of row r (work-group r), added in a fixed order.
 __global__ __launch_bounds__(256) void k_sum_partials(const double* partials, int count,
-                                                      double* result) {
+                                                      double* result, int accumulate) {
     __shared__ double wsum[4];
+    const double* p = partials + (uint64_t)blockIdx.x * count;
     double acc = 0.0;
-    for (int i = threadIdx.x; i < count; i += 256) acc += partials[i];
+    for (int i = threadIdx.x; i < count; i += 256) acc += p[i];
     acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
     __syncthreads();
-    if (threadIdx.x == 0) *result = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    if (threadIdx.x == 0) {
+        const double sum = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+        result[blockIdx.x] = accumulate ? result[blockIdx.x] + sum : sum;
+    }
+}
+
+void launch_sum_partials(const double* partials, int count, unsigned rows, double* result, bool accumulate,
+                         hipStream_t s) {
+    hipLaunchKernelGGL(k_sum_partials, dim3(rows), dim3(256), 0, s, partials, count, result, accumulate ? 1 : 0);
+    QSIM_HIPCHK(hipGetLastError());
 }
 
 double reduce_norm(const double2* st, int n, int bit, double* d_partials, double* d_result,
@@ -97,8 +102,7 @@ double reduce_norm(const double2* st, int n, int bit, double* d_partials, double
     const int blocks = (int)std::min<uint64_t>((count + 255) / 256, kReduceBlocks);
     hipLaunchKernelGGL(k_norm_partial, dim3(blocks), dim3(256), 0, s, st, count, bit, d_partials);
     QSIM_HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, s, d_partials, blocks, d_result);
-    QSIM_HIPCHK(hipGetLastError());
+    launch_sum_partials(d_partials, blocks, 1, d_result, false, s);
     double h = 0.0;
     QSIM_HIPCHK(hipMemcpyAsync(&h, d_result, sizeof(double), hipMemcpyDeviceToHost, s));
     QSIM_HIPCHK(hipStreamSynchronize(s));

@@ -1,0 +1,97 @@
+// Observable.cpp — PauliSum and the expectation-value methods of the simulators over the C ABI
+// (qsim_state_expectation / qsim_batch_expectation).  No reference counterpart.
+#include "qsim/Observable.hpp"
+
+#include <stdexcept>
+#include <string>
+
+#include "abi_util.hpp"
+#include "qsim/NoiseModel.hpp"
+#include "qsim/Simulator.hpp"
+#include "qsim/StateVector.hpp"
+#include "qsim_circuits.h"
+
+namespace qsim {
+
+using detail::check;
+
+PauliSum::PauliSum(int num_qubits) : num_qubits_(num_qubits) {
+    if (num_qubits < QSIM_MIN_QUBITS || num_qubits > QSIM_MAX_QUBITS_SINGLE)
+        throw std::invalid_argument("Number of qubits must be between 1 and 30");
+}
+
+PauliSum& PauliSum::add(double coeff, const std::vector<std::pair<int, char>>& factors) {
+    Term t{0, 0, coeff};
+    uint64_t seen = 0;
+    for (const auto& f : factors) {
+        const int q = f.first;
+        if (q < 0 || q >= num_qubits_)
+            throw std::out_of_range("Qubit index " + std::to_string(q) + " out of range");
+        const uint64_t bit = 1ull << q;
+        if (seen & bit) throw std::invalid_argument("Qubit " + std::to_string(q) + " repeated in a Pauli term");
+        seen |= bit;
+        switch (f.second) {
+            case 'X': t.x_mask |= bit; break;
+            case 'Y': t.x_mask |= bit; t.z_mask |= bit; break;
+            case 'Z': t.z_mask |= bit; break;
+            default: throw std::invalid_argument(std::string("Unknown Pauli letter '") + f.second + "'");
+        }
+    }
+    terms_.push_back(t);
+    return *this;
+}
+
+static std::vector<qsim_pauli_term> toAbi(const PauliSum& p, int num_qubits) {
+    if (p.getNumQubits() != num_qubits)
+        throw std::invalid_argument("Observable qubit count doesn't match simulator");
+    std::vector<qsim_pauli_term> v;
+    v.reserve(p.size());
+    for (const PauliSum::Term& t : p.terms()) v.push_back(qsim_pauli_term{t.x_mask, t.z_mask, t.coeff});
+    return v;
+}
+
+double StateVector::expectation(const PauliSum& observable) const {
+    const std::vector<qsim_pauli_term> terms = toAbi(observable, num_qubits_);
+    double e = 0.0;
+    check(qsim_state_expectation(h_, terms.data(), terms.size(), &e));
+    return e;
+}
+
+double Simulator::expectation(const PauliSum& observable) const { return state_.expectation(observable); }
+
+double NoisySimulator::expectation(const PauliSum& observable) const { return state_.expectation(observable); }
+
+std::vector<double> BatchedSimulator::getExpectations(const PauliSum& observable) {
+    const std::vector<qsim_pauli_term> terms = toAbi(observable, num_qubits_);
+    std::vector<double> e((size_t)batch_size_);
+    check(qsim_batch_expectation(h_, terms.data(), terms.size(), e.data()));
+    return e;
+}
+
+double BatchedSimulator::getAverageExpectation(const PauliSum& observable) {
+    const std::vector<double> e = getExpectations(observable);
+    double sum = 0.0;
+    for (double v : e) sum += v;
+    return sum / (double)e.size();
+}
+
+}  // namespace qsim
+
+extern "C" int qsim_pauli_term_make(int n_qubits, const int32_t* qubits, const char* letters, size_t count,
+                                    double coeff, qsim_pauli_term* out) {
+    try {
+        if (!out || (count && (!qubits || !letters))) throw std::invalid_argument("null buffer");
+        qsim::PauliSum p(n_qubits);
+        std::vector<std::pair<int, char>> factors;
+        for (size_t i = 0; i < count; ++i) factors.emplace_back(qubits[i], letters[i]);
+        p.add(coeff, factors);
+        *out = qsim_pauli_term{p.terms()[0].x_mask, p.terms()[0].z_mask, p.terms()[0].coeff};
+        return QSIM_OK;
+    } catch (const std::invalid_argument&) {
+        return QSIM_ERR_INVALID_ARGUMENT;
+    } catch (const std::out_of_range&) {
+        return QSIM_ERR_OUT_OF_RANGE;
+    } catch (const std::exception&) {
+        return QSIM_ERR_RUNTIME;
+    }
+}

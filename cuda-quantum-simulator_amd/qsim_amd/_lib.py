@@ -46,6 +46,10 @@ class qsim_noise_channel(Structure):
     _fields_ = [("type", c_int32), ("qubit", c_int32), ("probability", c_double)]
 
 
+class qsim_pauli_term(Structure):
+    _fields_ = [("x_mask", c_uint64), ("z_mask", c_uint64), ("coeff", c_double)]
+
+
 def _load(path: str) -> ctypes.CDLL:
     if not os.path.exists(path):
         raise ImportError(
@@ -127,6 +131,10 @@ _sig(hip, "qsim_state_collapse", [_P, c_int, c_int, c_double])
 _sig(hip, "qsim_state_sample", [_P, _P, c_int, _P])
 _sig(hip, "qsim_state_max_abs_diff", [_P, _P, POINTER(c_double)])
 _sig(hip, "qsim_state_memory_bytes", [_P, POINTER(c_uint64)])
+_sig(hip, "qsim_state_expectation", [_P, POINTER(qsim_pauli_term), c_size_t, POINTER(c_double)])
+_sig(hip, "qsim_batch_expectation", [_P, POINTER(qsim_pauli_term), c_size_t, POINTER(c_double)])
+_sig(hip, "qsim_expectation_plan", [c_int, POINTER(qsim_pauli_term), c_size_t, POINTER(c_int32), POINTER(c_int),
+                                    POINTER(c_int)])
 _sig(hip, "qsim_state_profile", [_P, c_int])
 _sig(hip, "qsim_state_profile_count", [_P, POINTER(c_int)])
 _sig(hip, "qsim_state_profile_get", [_P, c_int, c_char_p, c_size_t, POINTER(c_double),
@@ -146,6 +154,7 @@ _sig(hip, "qsim_batch_sample", [_P, _P, c_int, _P])
 _sig(hip, "qsim_state_last_run", [_P, _P, _P])
 _sig(hip, "qsim_batch_last_run", [_P, _P, _P])
 _sig(hip, "qsim_batch_histogram", [_P, _P, c_int, _P])
+_sig(hip, "qsim_batch_perm", [_P, POINTER(c_int32)])
 _sig(hip, "qsim_batch_device_ptr", [_P, POINTER(_P)])
 _sig(hip, "qsim_batch_sync", [_P])
 _sig(hip, "qsim_batch_profile", [_P, c_int])
@@ -239,6 +248,8 @@ _sig(api, "qsim_circuit_make", [c_int, c_int, c_int, c_uint, POINTER(qsim_gate),
                                 POINTER(c_size_t)])
 _sig(api, "qsim_circuit_depth", [c_int, POINTER(qsim_gate), c_size_t, POINTER(c_size_t)])
 _sig(api, "qsim_circuits_last_error", [], c_char_p)
+_sig(api, "qsim_pauli_term_make", [c_int, POINTER(c_int32), c_char_p, c_size_t, c_double,
+                                   POINTER(qsim_pauli_term)])
 
 
 def raise_for(rc: int, msg_fn=None) -> None:

@@ -151,6 +151,14 @@ class StateVector:
         _lib.check(_lib.hip.qsim_state_memory_bytes(self._h, _c.byref(b)))
         return b.value
 
+    def expectation(self, observable) -> float:
+        """<psi|H|psi> of a PauliSum, reduced on the device where the state lies: no readback and
+        no layout restore (qsim_state_expectation; no reference counterpart)."""
+        terms, count = observable.to_abi(self._n)
+        e = _c.c_double()
+        _lib.check(_lib.hip.qsim_state_expectation(self._h, terms, count, _c.byref(e)))
+        return e.value
+
     def probBitZero(self, bit: int) -> float:
         p = _c.c_double()
         _lib.check(_lib.hip.qsim_state_prob_bit_zero(self._h, bit, _c.byref(p)))
@@ -338,6 +346,8 @@ class Simulator:
         return self._state.sample(n_shots)
 
     def measureQubit(self, qubit: int) -> int: return self._state.measure(qubit)
+    # no reference counterpart: StateVector.expectation
+    def expectation(self, observable) -> float: return self._state.expectation(observable)
     def getNumQubits(self) -> int: return self._state.getNumQubits()
     def getStateSize(self) -> int: return self._state.getSize()
     def synchronize(self) -> None: self._state.synchronize()
@@ -483,6 +493,8 @@ class NoisySimulator:
         self._state.collapse(qubit, result, 1.0 / np.sqrt(kept))
         return result
 
+    # no reference counterpart: StateVector.expectation
+    def expectation(self, observable) -> float: return self._state.expectation(observable)
     def getNumQubits(self) -> int: return self._state.getNumQubits()
     def getStateSize(self) -> int: return self._state.getSize()
     def synchronize(self) -> None: self._state.synchronize()
@@ -577,6 +589,28 @@ class BatchedSimulator:
         out = np.empty(1 << self._n, dtype=np.complex128)
         _lib.check(_lib.hip.qsim_batch_traj_state(self._h, t, _ptr(out)))
         return out
+
+    def perm(self):
+        """Current logical -> physical qubit map inside every trajectory (qsim_batch_perm)."""
+        p = (_c.c_int32 * self._n)()
+        _lib.check(_lib.hip.qsim_batch_perm(self._h, p))
+        return list(p)
+
+    def getExpectations(self, observable) -> np.ndarray:
+        """Per-trajectory <psi_t|H|psi_t> of a PauliSum, reduced on the device
+        (qsim_batch_expectation; no reference counterpart)."""
+        terms, count = observable.to_abi(self._n)
+        out = np.empty(self._b, dtype=np.float64)
+        _lib.check(_lib.hip.qsim_batch_expectation(self._h, terms, count,
+                                                   out.ctypes.data_as(_c.POINTER(_c.c_double))))
+        return out
+
+    def getAverageExpectation(self, observable) -> float:
+        """Host mean of getExpectations, added in index order."""
+        total = 0.0
+        for v in self.getExpectations(observable):
+            total += float(v)
+        return total / self._b
 
     def sampleWith(self, uniforms: np.ndarray) -> np.ndarray:
         """Device sampling with given uniforms, shape (B, shots) trajectory-major; returns the

@@ -91,6 +91,8 @@ public:
     int getNumQubits() const { return state_.getNumQubits(); }
     size_t getStateSize() const { return state_.getSize(); }
     StateVector& state() { return state_; }
+    // <psi|H|psi> of a Pauli sum on the device (no reference counterpart; StateVector::expectation).
+    double expectation(const PauliSum& observable) const;
 
 private:
     StateVector state_;
@@ -132,6 +134,11 @@ public:
     std::vector<double> getProbabilities(int trajectory_idx) const;  // std::out_of_range
     std::vector<std::vector<int>> sample(int n_shots);                // [shot][trajectory]
     std::vector<int> getHistogram(int n_shots);
+    // Per-trajectory <psi_t|H|psi_t> of a Pauli sum, reduced on the device (no reference
+    // counterpart; qsim_batch_expectation), and their host mean in index order.
+    // std::invalid_argument on a qubit-count mismatch.
+    std::vector<double> getExpectations(const PauliSum& observable);
+    double getAverageExpectation(const PauliSum& observable);
 
     int getNumQubits() const { return num_qubits_; }
     int getBatchSize() const { return batch_size_; }

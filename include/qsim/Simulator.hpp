@@ -42,6 +42,8 @@ public:
 
     std::vector<int> sample(int n_shots);  // without collapse
     int measureQubit(int qubit);           // reference semantics: StateVector::measure (F2)
+    // <psi|H|psi> of a Pauli sum on the device (no reference counterpart; StateVector::expectation).
+    double expectation(const PauliSum& observable) const;
 
     int getNumQubits() const { return state_.getNumQubits(); }
     size_t getStateSize() const { return state_.getSize(); }

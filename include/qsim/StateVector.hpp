@@ -15,6 +15,8 @@ struct qsim_state;
 
 namespace qsim {
 
+class PauliSum;  // Observable.hpp
+
 // Layout of one device amplitude: interleaved {re, im} doubles (what devicePtr() points at).
 struct Amplitude {
     double re;
@@ -59,6 +61,10 @@ public:
     // (qsim_state_max_abs_diff / qsim_state_memory_bytes).
     double maxAbsDiff(const StateVector& other) const;
     size_t getDeviceMemoryBytes() const;
+    // <psi|H|psi> of a Pauli sum (Observable.hpp), reduced on the device where the state lies:
+    // no readback and no layout restore (qsim_state_expectation).  No reference counterpart.
+    // std::invalid_argument on a qubit-count mismatch.
+    double expectation(const PauliSum& observable) const;
     void assertNormalized(double tolerance = 1e-10) const;  // std::runtime_error
 
     // Reference semantics (src/StateVector.cu:260-314): measures index bit n-1-qubit

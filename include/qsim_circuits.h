@@ -31,6 +31,14 @@ int qsim_circuit_make(int kind, int n_qubits, int depth, unsigned int seed, qsim
 /* Circuit::getDepth() of a gate list (Circuit.cpp:183-201). */
 int qsim_circuit_depth(int n_qubits, const qsim_gate* gates, size_t count, size_t* depth);
 const char* qsim_circuits_last_error(void);
+/* One qsim::PauliSum::add (include/qsim/Observable.hpp) through the C ABI: the term coeff * the
+ * product of the `count` factors (qubits[i], letters[i] in "XYZ") on n_qubits qubits, with that
+ * method's argument checks (QSIM_ERR_OUT_OF_RANGE / QSIM_ERR_INVALID_ARGUMENT).  Part of the
+ * public interface of libqsim.so like the circuit factories above: it lets a non-C++ host build
+ * qsim_pauli_term masks with the C++ layer's checks (the Python tests reach PauliSum through it);
+ * it sets no message in qsim_circuits_last_error(). */
+int qsim_pauli_term_make(int n_qubits, const int32_t* qubits, const char* letters, size_t count,
+                         double coeff, qsim_pauli_term* out);
 
 #ifdef __cplusplus
 }

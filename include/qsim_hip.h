@@ -253,6 +253,31 @@ int qsim_state_max_abs_diff(qsim_state* a, qsim_state* b, double* out);
  * when the run does not keep a relayout plan), reduction and plan buffers, readout scratch. */
 int qsim_state_memory_bytes(qsim_state* s, uint64_t* bytes);
 
+/* ---- Pauli-sum expectation values (no reference counterpart: the reference has no observable
+ * API, a caller reads the amplitudes back) ----
+ * One term c * P of H = sum_t c_t P_t.  Bit q of x_mask: the factor on LOGICAL qubit q is X or Y;
+ * bit q of z_mask: it is Z or Y (Y sets both; neither: identity). */
+typedef struct qsim_pauli_term {
+    uint64_t x_mask, z_mask;
+    double coeff;
+} qsim_pauli_term;
+/* <psi|H|psi> by device reductions over the state where it lies: the masks are mapped through the
+ * state's current qubit layout on the host, so the layout (qsim_state_perm), a relayout plan's
+ * current buffer and the amplitudes are left exactly as they are.  Terms are grouped by x mask,
+ * one streaming read of the state per group (every Z/I-only term shares one); partial sums are
+ * added in a fixed order, so the value is bitwise reproducible.  A mask bit >= n ->
+ * QSIM_ERR_OUT_OF_RANGE; count == 0 -> 0.0 with no launch.  Synchronises.  A group of 16 or more
+ * terms evaluates the z bits above a work-group's 256-pair run once per run and term, the low
+ * bits per amplitude (QSIM_EXPECT_SPLIT=0: the whole sign per amplitude; the same weights added in
+ * the same order, so the same value). */
+int qsim_state_expectation(qsim_state* s, const qsim_pauli_term* terms, size_t count, double* out);
+/* Host-only (no GPU): the passes over the state (distinct physical x masks after duplicate
+ * strings are merged and zero coefficients dropped) and the kernel launches (a pass of more terms
+ * than one launch's table holds takes several) the lowering makes for these terms under the qubit
+ * layout perm (logical -> physical, n entries; null: identity). */
+int qsim_expectation_plan(int n_qubits, const qsim_pauli_term* terms, size_t count, const int32_t* perm,
+                          int* passes, int* launches);
+
 /* ---- timing (bench / profiling) ---- */
 /* Enable per-launch HIP-event timing on the state's stream; kernels are attributed by name. */
 int qsim_state_profile(qsim_state* s, int enable);
@@ -310,6 +335,11 @@ int qsim_batch_sample(qsim_batch* b, const double* uniforms, int shots, int64_t*
 /* BatchedSimulator::getHistogram (src/NoiseModel.cu:959-972): counts of the sampled outcomes
  * over every trajectory and shot, out-of-range outcomes skipped; hist has 2^n entries. */
 int qsim_batch_histogram(qsim_batch* b, const double* uniforms, int shots, int64_t* hist);
+/* qsim_state_expectation on every trajectory: per_traj[t] = <psi_t|H|psi_t>, t < B (no reference
+ * counterpart).  Carried Pauli frames are applied first; the qubit layout is left as it is. */
+int qsim_batch_expectation(qsim_batch* b, const qsim_pauli_term* terms, size_t count, double* per_traj);
+/* Current logical -> physical qubit map inside every trajectory, n entries (as qsim_state_perm). */
+int qsim_batch_perm(qsim_batch* b, int32_t* perm);
 int qsim_batch_device_ptr(qsim_batch* b, void** dptr);
 int qsim_batch_sync(qsim_batch* b);
 /* Last fused batched run: tile passes and how many ran as circuit-specialised kernels. */

@@ -458,8 +458,43 @@ double reduce_max_abs_diff(const double2* a, const double2* b, int n, double* d_
 struct Scratch;
 void launch_histogram(const int64_t* d_idx, uint64_t count, uint64_t N, unsigned long long* d_hist,
                       hipStream_t s);
+// Host-only: chunk CDF of `sums` + per-shot (chunk, residual target); chunk -1: past the end.
+void chunk_targets(const double* sums, uint64_t nchunks, const double* uniforms, int shots,
+                   int64_t* chunk_of, double* target);
 void sample_indices(const double2* st, int n, uint64_t batch, const double* uniforms, int shots,
                     int64_t* out, hipStream_t s, Scratch& scratch);
+// ---- readout of a sharded state (dist_readout.hip; the collectives around it: dist.hip) ----
+// A chunk: the 2^c amplitudes sharing all logical index bits >= c, c = min(kDistChunkLog, L).
+constexpr int kDistChunkLog = 12;
+int dist_chunk_log(int L);
+// Logical qubits below c that sit on a rank position (the sampler brings them local first).
+uint64_t dist_localize_mask(int n, int L, int c, const int* perm);
+// How one shard's chunks map to the state's: amask = the local positions of logical qubits
+// 0 .. c-1 (pos[k]: of qubit k); a shard's chunk slot j numbers its chunks by the other local
+// positions in ascending order, slot bit k landing on bit dst[k] of the global (logical) chunk id;
+// rank_or: the id bits fixed by the shard's rank.
+struct ChunkMap {
+    int L, c;
+    uint64_t amask, rank_or;
+    int8_t dst[64];
+    int8_t pos[kDistChunkLog];
+};
+ChunkMap make_chunk_map(int n, int L, int c, int rank, const int* perm);
+// One shot's in-chunk search: the chunk's local offset (amask bits 0), its logical index bits
+// >= c (hi), the residual target and where the result goes.
+struct ShotJob {
+    uint64_t base, hi;
+    double target;
+    int64_t shot;
+};
+// Doubles of partial sums launch_dist_chunk_sums needs for this map (d_partials).
+size_t dist_chunk_partials_count(const ChunkMap& m, int* splits_log_out = nullptr);
+// d_sums[global chunk id] = sum of |a|^2 over the chunk, for every chunk of shard `st`.
+void launch_dist_chunk_sums(const double2* st, const ChunkMap& m, uint64_t nchunks, double* d_partials,
+                            double* d_sums, hipStream_t s);
+// d_out[job.shot] = (double)(job.hi | first in-chunk index whose prefix reaches job.target).
+void launch_dist_chunk_search(const double2* st, const ChunkMap& m, const ShotJob* d_jobs, int count, int shots,
+                              double* d_out, hipStream_t s);
 // Average of |a|^2 over `batch` trajectories into out[2^n] (device).
 void launch_avg_probabilities(const double2* st, int n, uint64_t batch, double* out,
                               hipStream_t s);

@@ -258,6 +258,35 @@ __global__ __launch_bounds__(64) void k_chunk_search(const double2* st, uint64_t
     }
 }
 
+// Host step of the sampler, shared by the single-state path below and the sharded one (dist.hip):
+// the chunk CDF (Neumaier-compensated prefix of `sums`), then per shot the chunk lower_bound finds
+// and the residual target inside it; chunk -1 (target 0): the uniform lies past the end.
+void chunk_targets(const double* sums, uint64_t nchunks, const double* uniforms, int shots,
+                   int64_t* chunk_of, double* target) {
+    std::vector<double> cdf(nchunks), comp(nchunks);
+    double run = 0.0, c = 0.0;  // Neumaier: run + c is the prefix to ~1 ulp
+    for (uint64_t k = 0; k < nchunks; ++k) {
+        const double x = sums[k];
+        const double y = run + x;
+        c += std::fabs(run) >= std::fabs(x) ? (run - y) + x : (x - y) + run;
+        run = y;
+        cdf[k] = run + c;
+        comp[k] = c - (cdf[k] - run);  // residual below cdf[k]
+    }
+    for (int i = 0; i < shots; ++i) {
+        const double r = uniforms[i];
+        auto it = std::lower_bound(cdf.begin(), cdf.end(), r);
+        if (it == cdf.end()) {
+            chunk_of[i] = -1;
+            target[i] = 0.0;
+        } else {
+            const int64_t k = it - cdf.begin();
+            chunk_of[i] = k;
+            target[i] = k > 0 ? (r - cdf[k - 1]) - comp[k - 1] : r;
+        }
+    }
+}
+
 // Shots of `batch` trajectories (the single state is batch = 1).  uniforms / out are
 // trajectory-major: shot s of trajectory t at t * shots + s (the reference draws them in that
 // order, src/NoiseModel.cu:938-957).  The chunk prefix is accumulated with Neumaier's
@@ -284,31 +313,14 @@ void sample_indices(const double2* st, int n, uint64_t batch, const double* unif
     QSIM_HIPCHK(hipMemcpyAsync(sums.data(), d_sums, all_chunks * sizeof(double),
                                hipMemcpyDeviceToHost, s));
     QSIM_HIPCHK(hipStreamSynchronize(s));
-    std::vector<double> cdf(nchunks), comp(nchunks);
     std::vector<int64_t> chunk_of(nshots);
     std::vector<double> target(nshots);
     for (uint64_t t = 0; t < batch; ++t) {
-        double run = 0.0, c = 0.0;  // Neumaier: run + c is the prefix to ~1 ulp
-        for (uint64_t k = 0; k < nchunks; ++k) {
-            const double x = sums[t * nchunks + k];
-            const double y = run + x;
-            c += std::fabs(run) >= std::fabs(x) ? (run - y) + x : (x - y) + run;
-            run = y;
-            cdf[k] = run + c;
-            comp[k] = c - (cdf[k] - run);  // residual below cdf[k]
-        }
-        for (int i = 0; i < shots; ++i) {
-            const uint64_t j = t * (uint64_t)shots + (uint64_t)i;
-            const double r = uniforms[j];
-            auto it = std::lower_bound(cdf.begin(), cdf.end(), r);
-            if (it == cdf.end()) {
-                chunk_of[j] = -1;
-                target[j] = 0.0;
-            } else {
-                const int64_t k = it - cdf.begin();
-                chunk_of[j] = (int64_t)(t * nchunks) + k;
-                target[j] = k > 0 ? (r - cdf[k - 1]) - comp[k - 1] : r;
-            }
+        chunk_targets(sums.data() + t * nchunks, nchunks, uniforms + t * (uint64_t)shots, shots,
+                      chunk_of.data() + t * (uint64_t)shots, target.data() + t * (uint64_t)shots);
+        for (int i = 0; i < shots; ++i) {  // chunk ids are global over the batch
+            int64_t& k = chunk_of[t * (uint64_t)shots + (uint64_t)i];
+            if (k >= 0) k += (int64_t)(t * nchunks);
         }
     }
     QSIM_HIPCHK(hipMemcpyAsync(d_chunk, chunk_of.data(), nshots * sizeof(int64_t),

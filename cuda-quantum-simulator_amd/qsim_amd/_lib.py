@@ -225,6 +225,12 @@ _sig(hip, "qsim_dist_local_state", [_P, _P])
 _sig(hip, "qsim_dist_gather_state", [_P, _P])
 _sig(hip, "qsim_dist_total_probability", [_P, POINTER(c_double)])
 _sig(hip, "qsim_dist_prob_bit_zero", [_P, c_int, POINTER(c_double)])
+_sig(hip, "qsim_dist_bcast", [_P, _P, c_size_t])
+_sig(hip, "qsim_dist_probabilities", [_P, _P])
+_sig(hip, "qsim_dist_sample", [_P, _P, c_int, _P])
+_sig(hip, "qsim_dist_collapse", [_P, c_int, c_int, c_double])
+_sig(hip, "qsim_dist_measure", [_P, c_int, c_double, POINTER(c_int)])
+_sig(hip, "qsim_dist_sample_plan", [c_int, c_int, POINTER(c_int32), POINTER(c_int), POINTER(c_uint64)])
 _sig(hip, "qsim_dist_profile", [_P, c_int])
 _sig(hip, "qsim_dist_profile_count", [_P, POINTER(c_int)])
 _sig(hip, "qsim_dist_profile_get", [_P, c_int, c_char_p, c_size_t, POINTER(c_double),

@@ -177,6 +177,64 @@ class DistributedSimulator:
         _lib.check(_lib.hip.qsim_dist_prob_bit_zero(self._h, q, _c.byref(t)))
         return t.value
 
+    # -- readout without a gather of amplitudes (collective: every rank calls with the same
+    #    arguments; the semantics are StateVector's)
+    def getProbabilities(self) -> Optional[np.ndarray]:
+        """|a_i|^2 in logical index order on rank 0 (collective); None on other ranks."""
+        root = self._virtual or self._rank == 0
+        out = np.empty(1 << self._n, dtype=np.float64) if root else None
+        _lib.check(_lib.hip.qsim_dist_probabilities(self._h, out.ctypes.data_as(_c.c_void_p)
+                                                    if root else None))
+        return out
+
+    def setSeed(self, seed: int) -> None:
+        """Seed this rank's generator (StateVector.setSeed).  sample / measure* draw on rank 0 and
+        broadcast, so the shots are rank 0's; with the same seed on every rank all generators
+        also stay in step."""
+        self._rng = np.random.default_rng(seed)
+
+    def _uniforms(self, k: int) -> np.ndarray:
+        rng = getattr(self, "_rng", None)
+        u = np.ascontiguousarray((rng if rng is not None else np.random.default_rng()).random(k))
+        _lib.check(_lib.hip.qsim_dist_bcast(self._h, u.ctypes.data_as(_c.c_void_p), u.size))
+        return u
+
+    def sampleWith(self, uniforms) -> np.ndarray:
+        """StateVector.sampleWith on the sharded state: every rank passes the same uniforms and
+        gets all the shots.  May change the qubit map (perm()): the logical qubits of a sampling
+        chunk are brought to local positions first; the amplitudes are untouched."""
+        u = np.ascontiguousarray(uniforms, dtype=np.float64)
+        if u.size <= 0:
+            raise ValueError("n_shots must be positive")
+        out = np.empty(u.size, dtype=np.int64)
+        _lib.check(_lib.hip.qsim_dist_sample(self._h, u.ctypes.data_as(_c.c_void_p), int(u.size),
+                                             out.ctypes.data_as(_c.c_void_p)))
+        return out
+
+    def sample(self, n_shots: int) -> np.ndarray:
+        if n_shots <= 0:
+            raise ValueError("n_shots must be positive")
+        return self.sampleWith(self._uniforms(n_shots))
+
+    def collapse(self, bit: int, result: int, scale: float) -> None:
+        _lib.check(_lib.hip.qsim_dist_collapse(self._h, bit, result, scale))
+
+    def measureBit(self, bit: int, uniform: Optional[float] = None) -> int:
+        """StateVector.measureBit; `uniform`: the draw to use (the same on every rank) instead
+        of one from rank 0's generator."""
+        if bit < 0 or bit >= self._n:
+            raise ValueError(f"Qubit index {bit} out of range [0, {self._n - 1}]")
+        u = float(self._uniforms(1)[0]) if uniform is None else float(uniform)
+        r = _c.c_int(0)
+        _lib.check(_lib.hip.qsim_dist_measure(self._h, bit, u, _c.byref(r)))
+        return r.value
+
+    def measureQubit(self, qubit: int, uniform: Optional[float] = None) -> int:
+        """Reference semantics: big-endian index bit n-1-qubit (F2, as StateVector.measure)."""
+        if qubit < 0 or qubit >= self._n:
+            raise ValueError(f"Qubit index {qubit} out of range [0, {self._n - 1}]")
+        return self.measureBit(self._n - 1 - qubit, uniform)
+
     def profile(self, enable: bool = True) -> None:
         _lib.check(_lib.hip.qsim_dist_profile(self._h, 1 if enable else 0))
 
@@ -222,6 +280,17 @@ def plan(circuit: Circuit, world: int, rank: int, perm: Optional[List[int]] = No
             out_steps.append({"kind": "ops", "ops": out_ops[s.op_begin:s.op_end],
                               "role": s.role, "pivot": s.pivot})
     return out_steps, list(p)
+
+
+def sample_plan(n: int, world: int, perm: List[int]) -> Tuple[int, int]:
+    """Host-only (qsim_dist_sample_plan): (chunk_log, localize_mask) of sampling a sharded state
+    whose qubit map is `perm` — the chunk size and the logical qubits brought local first."""
+    p = (_c.c_int32 * len(perm))(*perm)
+    if len(perm) != n:
+        raise ValueError("perm needs one entry per qubit")
+    c, m = _c.c_int(0), _c.c_uint64(0)
+    _lib.check(_lib.hip.qsim_dist_sample_plan(n, world, p, _c.byref(c), _c.byref(m)))
+    return c.value, m.value
 
 
 def plan_memo_clear() -> None:

@@ -1,0 +1,76 @@
+// DistributedSimulator.hpp — the state sharded over the GPUs of one node, one process per GPU
+// (qsim_dist_* of qsim_hip.h; no reference counterpart: the reference is single-GPU).
+//
+// `Simulator`'s run / readout / sampling / measurement signatures and exception types on a
+// sharded state.  Every method that touches the state is collective: every rank calls it with
+// the same arguments.  Gathered readouts (getStateVector, getProbabilities) return the result on
+// rank 0 and an empty vector elsewhere; sample() and measureQubit() return the same values on
+// every rank (rank 0 draws the uniforms and broadcasts them).  sample() gathers nothing, but may
+// move qubits between rank and local positions (the amplitudes are unchanged).
+//
+//   rank 0:  auto id = DistributedSimulator::uniqueId();   // then hand `id` to the other ranks
+//   rank r:  DistributedSimulator sim(30, r, 8, id, /*device=*/r);
+//
+// makeVirtual(n, world) keeps all `world` shards in this process on one GPU (exchanges by device
+// copies): the same planner and kernels, for running the sharded path on a single GPU.
+#pragma once
+
+#include <array>
+#include <complex>
+#include <random>
+#include <vector>
+
+#include "Circuit.hpp"
+#include "Simulator.hpp"
+
+struct qsim_dist;
+
+namespace qsim {
+
+class DistributedSimulator {
+public:
+    using UniqueId = std::array<unsigned char, 128>;
+
+    DistributedSimulator(int num_qubits, int rank, int world, const UniqueId& unique_id, int device);
+    ~DistributedSimulator();
+    DistributedSimulator(DistributedSimulator&& o) noexcept;
+    DistributedSimulator& operator=(DistributedSimulator&& o) noexcept;
+    DistributedSimulator(const DistributedSimulator&) = delete;
+    DistributedSimulator& operator=(const DistributedSimulator&) = delete;
+
+    static UniqueId uniqueId();  // on rank 0
+    static DistributedSimulator makeVirtual(int num_qubits, int world, int device = 0);
+
+    void reset();
+    void run(const Circuit& circuit);  // std::invalid_argument on qubit-count mismatch
+    void runSequence(const std::vector<Circuit>& circuits);
+
+    std::vector<std::complex<double>> getStateVector() const;  // rank 0; empty elsewhere
+    std::vector<double> getProbabilities() const;              // rank 0; empty elsewhere
+
+    std::vector<int> sample(int n_shots);  // without collapse; the same shots on every rank
+    int measureQubit(int qubit);           // reference semantics: index bit n-1-qubit (F2)
+
+    int getNumQubits() const { return num_qubits_; }
+    int getWorldSize() const { return world_; }
+    int getRank() const { return rank_; }
+
+    void setRunMode(RunMode m) { mode_ = m; }
+    RunMode getRunMode() const { return mode_; }
+    void setSeed(unsigned int seed);
+    void synchronize() const;
+
+private:
+    DistributedSimulator() = default;
+    std::vector<double> uniforms(int count);
+    bool root() const { return virtual_ || rank_ == 0; }
+
+    qsim_dist* h_ = nullptr;
+    int num_qubits_ = 0, rank_ = 0, world_ = 1;
+    bool virtual_ = false;
+    RunMode mode_ = RunMode::Fused;
+    bool seeded_ = false;
+    std::mt19937 rng_;
+};
+
+}  // namespace qsim

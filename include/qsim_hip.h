@@ -498,6 +498,32 @@ int qsim_dist_local_state(qsim_dist* d, double* dst);
 int qsim_dist_gather_state(qsim_dist* d, double* dst);
 int qsim_dist_total_probability(qsim_dist* d, double* out); /* collective */
 int qsim_dist_prob_bit_zero(qsim_dist* d, int logical_bit, double* out);  /* collective */
+/* ---- readout of the sharded state.  Every entry below is collective: every rank calls it with
+ * the same arguments (virtual objects: one call covers all shards). ---- */
+/* Rank 0's `count` doubles go to every rank (RCCL: ncclBroadcast; hosted: posts; virtual and
+ * world 1: nothing to do).  How one host random draw becomes the same on every rank. */
+int qsim_dist_bcast(qsim_dist* d, double* buf, size_t count);
+/* 2^n doubles |a_i|^2 in LOGICAL index order on rank 0 (dst may be NULL on other ranks).  |a|^2
+ * is computed per shard on the device, so 8 B per amplitude are gathered, not 16. */
+int qsim_dist_probabilities(qsim_dist* d, double* dst);
+/* qsim_state_sample on the sharded state: out[s] = lower_bound of uniforms[s] over the CDF in
+ * logical index order, 2^n past the end; every rank passes the same uniforms and receives all
+ * `shots` indices.  Nothing is gathered: per-chunk sums of |a|^2 (chunks of 2^min(12, L) logical
+ * indices) are all-reduced, each shot's chunk is searched on the rank that owns it.  If one of
+ * the chunk's logical qubits sits on a rank position, one remap brings them local first: the
+ * amplitudes are unchanged, but the qubit map (qsim_dist_perm) may differ afterwards.
+ * shots <= 0 returns at once. */
+int qsim_dist_sample(qsim_dist* d, const double* uniforms, int shots, int64_t* out);
+/* Zero the amplitudes whose logical bit != result and scale the rest (qsim_state_collapse). */
+int qsim_dist_collapse(qsim_dist* d, int logical_bit, int result, double scale);
+/* Measure a logical bit with the caller's uniform u (the same on every rank): result = u < p0 ?
+ * 0 : 1 with p0 = qsim_dist_prob_bit_zero, then collapse with scale 1 / sqrt(p(result)).  An
+ * outcome of probability below 1e-15 fails with QSIM_ERR_RUNTIME. */
+int qsim_dist_measure(qsim_dist* d, int logical_bit, double u, int* result);
+/* Host-only: what qsim_dist_sample would do for qubit map `perm` (n entries): the chunk size
+ * (log2) and the set of logical qubits it must bring local first (0: no remap). */
+int qsim_dist_sample_plan(int n_qubits, int world, const int32_t* perm, int* chunk_log,
+                          uint64_t* localize_mask);
 int qsim_dist_profile(qsim_dist* d, int enable);
 int qsim_dist_profile_count(qsim_dist* d, int* n);
 int qsim_dist_profile_get(qsim_dist* d, int i, char* name, size_t name_len, double* total_ms,

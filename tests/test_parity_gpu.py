@@ -7,6 +7,8 @@ Mirrors the reference suites:
                                        compared on probabilities at 1e-10 (:273)
   tests/test_gate_algebra.cu        -> identities up to global phase at 1e-12 (:33)
   tests/test_optimized_gates.cu     -> every target on random normalized states, n = 8/10/16
+The per-gate kernels' operand classes and launch variants, one gate at a time against a dense
+numpy reference with bit-identity outside the gate's subspace: tests/test_pergate_matrix_gpu.py.
 Tolerance: the north_star bound |amp_gpu - amp_ref|^2 < 1e-10 is implied by the 1e-12
 component bound used here.
 """

@@ -518,6 +518,11 @@ struct ExpectPlan {
     size_t launches = 0;
 };
 ExpectPlan lower_expectation(int n, const qsim_pauli_term* terms, size_t count, const int* perm);
+// The merge-and-group step shared by lower_expectation and lower_pauli_apply (adjoint.hip):
+// weight(x, z, c, e) fills e.cr / e.ci of the merged term c * (physical x, z); e.z is set, the
+// weights start at 0.
+ExpectPlan lower_pauli_terms(int n, const qsim_pauli_term* terms, size_t count, const int* perm,
+                             const std::function<void(uint64_t, uint64_t, double, ExpectTerm&)>& weight);
 size_t expect_chunks(uint64_t batch);  // partials per trajectory a launch may write
 // d_out[t] = the plan's sum on trajectory t of st ([batch][2^n]); terms: the owner's device copy of
 // the term table (uploaded here), d_partials: batch * expect_chunks(batch) doubles.  Nothing is
@@ -527,6 +532,30 @@ void launch_expectation(const double2* st, int n, uint64_t batch, const ExpectPl
                         double* d_partials, double* d_out, hipStream_t s, Timer* tm);
 // The z lane/run split of groups of at least kExpectSplitMin terms (QSIM_EXPECT_SPLIT, default 1).
 constexpr int kExpectSplitMin = 16;
+
+// Adjoint-method gradients (adjoint.hip).  A rotation's generator: pauli = 1 X, 2 Y, 3 Z on
+// position t (0: the identity, a plain inner product), times |1><1| on position c when c >= 0.
+struct Generator {
+    int pauli = 0, t = -1, c = -1;
+};
+bool gate_is_parameterised(int type);
+qsim_gate gate_inverse(const qsim_gate& g);    // S <-> Sdag, T <-> Tdag, rotations: angle negated
+Generator gate_generator(const qsim_gate& g);  // of a parameterised gate, on the gate's own qubits
+bool adjoint_fused_on();                       // QSIM_ADJOINT_FUSED (default 1), read at every call
+// The terms of dst = H src, merged and grouped by physical x mask like lower_expectation; a term's
+// (cr, ci) is its complex weight c (-i)^nY (the kernel adds the sign (-1)^popcount(i & z)).
+ExpectPlan lower_pauli_apply(int n, const qsim_pauli_term* terms, size_t count, const int* perm);
+// dst = H src out of place (src != dst), one streaming pass per launch of the plan; an empty plan
+// zeroes dst.  terms: the owner's device copy of the term table.  Asynchronous.
+void launch_pauli_apply(const double2* src, double2* dst, int n, const ExpectPlan& plan, DevBuf& terms,
+                        hipStream_t s, Timer* tm);
+// *d_re + i *d_im = <a| G |b> (either may be null), d_partials: 2 * expect_chunks(1) doubles.
+void launch_braket(const double2* a, const double2* b, int n, const Generator& g, double* d_partials, double* d_re,
+                   double* d_im, hipStream_t s, Timer* tm);
+// *d_out = Im <lam| G |phi>, then inv (the lowered inverse of the rotation: K_M1 or K_DIAG on g's
+// target and control) applied to both states, in one launch.
+void launch_adjoint_step(double2* phi, double2* lam, int n, const Generator& g, const Op& inv, double* d_partials,
+                         double* d_out, hipStream_t s, Timer* tm);
 
 // ---------------------------------------------------------------------------------------
 // Timing (capi.hip): per-launch HIP events grouped by kernel name.

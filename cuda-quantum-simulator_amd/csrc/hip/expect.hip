@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <utility>
 #include <vector>
@@ -30,7 +31,8 @@
 
 namespace qsim_hip {
 
-ExpectPlan lower_expectation(int n, const qsim_pauli_term* terms, size_t count, const int* perm) {
+ExpectPlan lower_pauli_terms(int n, const qsim_pauli_term* terms, size_t count, const int* perm,
+                             const std::function<void(uint64_t, uint64_t, double, ExpectTerm&)>& weight) {
     if (n < 1 || n > 63) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
     if (count && !terms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
     if (perm) {
@@ -64,7 +66,19 @@ ExpectPlan lower_expectation(int n, const qsim_pauli_term* terms, size_t count, 
         if (plan.groups.empty() || plan.groups.back().x != x) {
             plan.groups.push_back(ExpectGroup{x, plan.terms.size(), plan.terms.size()});
         }
-        ExpectTerm e{z, c, 0.0};
+        ExpectTerm e{z, 0.0, 0.0};
+        weight(x, z, c, e);
+        plan.terms.push_back(e);
+        plan.groups.back().end = plan.terms.size();
+    }
+    for (const ExpectGroup& g : plan.groups)
+        plan.launches += (g.end - g.begin + kExpectTerms - 1) / kExpectTerms;
+    return plan;
+}
+
+ExpectPlan lower_expectation(int n, const qsim_pauli_term* terms, size_t count, const int* perm) {
+    return lower_pauli_terms(n, terms, count, perm, [](uint64_t x, uint64_t z, double c, ExpectTerm& e) {
+        e.cr = c;
         if (x != 0) {
             const int ny = __builtin_popcountll(x & z);
             if (ny & 1) {
@@ -74,12 +88,7 @@ ExpectPlan lower_expectation(int n, const qsim_pauli_term* terms, size_t count, 
                 e.cr = (ny / 2) & 1 ? -2.0 * c : 2.0 * c;
             }
         }
-        plan.terms.push_back(e);
-        plan.groups.back().end = plan.terms.size();
-    }
-    for (const ExpectGroup& g : plan.groups)
-        plan.launches += (g.end - g.begin + kExpectTerms - 1) / kExpectTerms;
-    return plan;
+    });
 }
 
 size_t expect_chunks(uint64_t batch) {

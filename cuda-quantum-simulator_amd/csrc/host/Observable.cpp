@@ -59,6 +59,31 @@ double StateVector::expectation(const PauliSum& observable) const {
 
 double Simulator::expectation(const PauliSum& observable) const { return state_.expectation(observable); }
 
+void StateVector::applyPauliSum(const PauliSum& observable, StateVector& dst) const {
+    const std::vector<qsim_pauli_term> terms = toAbi(observable, num_qubits_);
+    check(qsim_state_apply_pauli_sum(h_, dst.h_, terms.data(), terms.size()));
+}
+
+std::complex<double> StateVector::innerProduct(const StateVector& other) const {
+    double out[2] = {0.0, 0.0};
+    check(qsim_state_inner_product(h_, other.h_, out));
+    return {out[0], out[1]};
+}
+
+Gradient Simulator::gradient(const Circuit& circuit, const PauliSum& observable, RunMode mode) {
+    if (circuit.getNumQubits() != state_.getNumQubits())
+        throw std::invalid_argument("Circuit qubit count doesn't match simulator");
+    const std::vector<qsim_pauli_term> terms = toAbi(observable, state_.getNumQubits());
+    const std::vector<qsim_gate> gates = detail::toAbi(circuit);
+    Gradient g{0.0, std::vector<double>(gates.size(), 0.0)};
+    check(qsim_state_gradient(state_.handle(), gates.data(), gates.size(), terms.data(), terms.size(),
+                              mode == RunMode::Fused ? QSIM_RUN_FUSED : QSIM_RUN_PER_GATE, &g.value,
+                              g.gradient.data()));
+    return g;
+}
+
+void Simulator::releaseGradientBuffers() { check(qsim_state_gradient_release(state_.handle())); }
+
 double NoisySimulator::expectation(const PauliSum& observable) const { return state_.expectation(observable); }
 
 std::vector<double> BatchedSimulator::getExpectations(const PauliSum& observable) {

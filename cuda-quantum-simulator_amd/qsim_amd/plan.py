@@ -146,6 +146,32 @@ def plan_relayout(circuit: Circuit):
     return list(perm), passes.value, pred.value
 
 
+def gate_inverse(op):
+    """The inverse of one GateOp (qsim_gate_inverse, host only): self-inverse types unchanged,
+    S <-> Sdag, T <-> Tdag, rotations with the angle negated."""
+    from .circuit import GateOp, GateType
+    g, out = _lib.qsim_gate(), _lib.qsim_gate()
+    g.type = int(op.type)
+    g.nqubits = len(op.qubits)
+    for j, q in enumerate(op.qubits):
+        g.qubits[j] = q
+    g.parameter = op.parameter
+    _lib.check(_lib.hip.qsim_gate_inverse(ctypes.byref(g), ctypes.byref(out)))
+    return GateOp(GateType(out.type), [out.qubits[j] for j in range(out.nqubits)], out.parameter)
+
+
+def gradient_plan(circuit: Circuit, observable):
+    """(parameterised gates, inverted non-parameterised segments, Pauli-sum apply passes) of the
+    backward sweep Simulator.gradient would run (qsim_gradient_plan, host only)."""
+    n = circuit.getNumQubits()
+    arr, cnt = circuit.to_abi()
+    terms, nterms = observable.to_abi(n)
+    p, s, a = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.hip.qsim_gradient_plan(n, arr, cnt, terms, nterms, ctypes.byref(p), ctypes.byref(s),
+                                           ctypes.byref(a)))
+    return p.value, s.value, a.value
+
+
 def jit_build_relayout(circuit: Circuit) -> int:
     """Compile the circuit's relayout plan (qsim_jit_build_relayout, hipRTC for gfx950, no GPU
     needed); returns the code-object size in bytes."""

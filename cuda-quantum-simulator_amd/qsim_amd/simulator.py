@@ -159,6 +159,18 @@ class StateVector:
         _lib.check(_lib.hip.qsim_state_expectation(self._h, terms, count, _c.byref(e)))
         return e.value
 
+    def applyPauliSum(self, observable, dst: "StateVector") -> None:
+        """dst = H |self> out of place on the device (qsim_state_apply_pauli_sum); dst takes this
+        state's qubit layout.  ValueError when dst is self or of another size."""
+        terms, count = observable.to_abi(self._n)
+        _lib.check(_lib.hip.qsim_state_apply_pauli_sum(self._h, dst._h, terms, count))
+
+    def innerProduct(self, other: "StateVector") -> complex:
+        """<self|other> by a fixed-order device reduction (qsim_state_inner_product)."""
+        out = (_c.c_double * 2)()
+        _lib.check(_lib.hip.qsim_state_inner_product(self._h, other._h, out))
+        return complex(out[0], out[1])
+
     def probBitZero(self, bit: int) -> float:
         p = _c.c_double()
         _lib.check(_lib.hip.qsim_state_prob_bit_zero(self._h, bit, _c.byref(p)))
@@ -348,6 +360,29 @@ class Simulator:
     def measureQubit(self, qubit: int) -> int: return self._state.measure(qubit)
     # no reference counterpart: StateVector.expectation
     def expectation(self, observable) -> float: return self._state.expectation(observable)
+
+    def gradient(self, circuit: Circuit, observable, mode: RunMode = RunMode.Fused):
+        """(value, gradient): runs `circuit` on the state as it is, as run() would in `mode`, then
+        <psi|H|psi> and its derivative with respect to the angle of every gate (numpy array, one
+        entry per gate, 0 for a gate without a parameter) by the adjoint method: one backward
+        sweep on the device, one pass over two work states per angle, instead of two circuit runs
+        per angle (qsim_state_gradient; no reference counterpart).  The state is left as run()
+        leaves it."""
+        n = self._state.getNumQubits()
+        if circuit.getNumQubits() != n:
+            raise ValueError("Circuit qubit count doesn't match simulator")
+        arr, cnt = circuit.to_abi()
+        terms, nterms = observable.to_abi(n)
+        value = _c.c_double()
+        grad = np.zeros(max(1, cnt), dtype=np.float64)
+        _lib.check(_lib.hip.qsim_state_gradient(self._state.handle, arr, cnt, terms, nterms, int(mode),
+                                                _c.byref(value), grad.ctypes.data_as(_c.POINTER(_c.c_double))))
+        return value.value, grad[:cnt]
+
+    def releaseGradientBuffers(self) -> None:
+        """Free the two work states gradient() keeps on the state between calls."""
+        _lib.check(_lib.hip.qsim_state_gradient_release(self._state.handle))
+
     def getNumQubits(self) -> int: return self._state.getNumQubits()
     def getStateSize(self) -> int: return self._state.getSize()
     def synchronize(self) -> None: self._state.synchronize()

@@ -25,6 +25,12 @@ namespace qsim {
 
 enum class RunMode { PerGate, Fused };
 
+// Result of Simulator::gradient: the expectation value and dE/dtheta per gate of the circuit.
+struct Gradient {
+    double value;
+    std::vector<double> gradient;
+};
+
 class Simulator {
 public:
     explicit Simulator(int num_qubits);
@@ -44,6 +50,14 @@ public:
     int measureQubit(int qubit);           // reference semantics: StateVector::measure (F2)
     // <psi|H|psi> of a Pauli sum on the device (no reference counterpart; StateVector::expectation).
     double expectation(const PauliSum& observable) const;
+    // Runs `circuit` on the state as it is (as run() would, in `mode`), then returns <psi|H|psi>
+    // and its derivative with respect to the angle of every gate (one entry per gate, 0 for a gate
+    // without a parameter) by the adjoint method: one backward sweep on the device, one pass over
+    // two work states per angle, instead of two circuit runs per angle (qsim_state_gradient).
+    // The state is left as run() leaves it.  std::invalid_argument on a qubit-count mismatch; no
+    // reference counterpart.
+    Gradient gradient(const Circuit& circuit, const PauliSum& observable, RunMode mode = RunMode::Fused);
+    void releaseGradientBuffers();  // free the two work states gradient() keeps between calls
 
     int getNumQubits() const { return state_.getNumQubits(); }
     size_t getStateSize() const { return state_.getSize(); }

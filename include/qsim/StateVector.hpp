@@ -65,6 +65,12 @@ public:
     // no readback and no layout restore (qsim_state_expectation).  No reference counterpart.
     // std::invalid_argument on a qubit-count mismatch.
     double expectation(const PauliSum& observable) const;
+    // dst = H |this> out of place on the device (qsim_state_apply_pauli_sum); dst takes this
+    // state's qubit layout.  std::invalid_argument on a qubit-count mismatch or &dst == this.
+    void applyPauliSum(const PauliSum& observable, StateVector& dst) const;
+    // <this|other> by a fixed-order device reduction (qsim_state_inner_product): bitwise
+    // reproducible; innerProduct(*this) is the norm.  std::invalid_argument on a size mismatch.
+    std::complex<double> innerProduct(const StateVector& other) const;
     void assertNormalized(double tolerance = 1e-10) const;  // std::runtime_error
 
     // Reference semantics (src/StateVector.cu:260-314): measures index bit n-1-qubit

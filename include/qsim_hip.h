@@ -278,6 +278,43 @@ int qsim_state_expectation(qsim_state* s, const qsim_pauli_term* terms, size_t c
 int qsim_expectation_plan(int n_qubits, const qsim_pauli_term* terms, size_t count, const int32_t* perm,
                           int* passes, int* launches);
 
+/* ---- adjoint-method gradients of <psi|H|psi> (no reference counterpart) ----
+ * dst = H src out of place, one streaming pass per group of terms sharing an x mask (same qubit
+ * count and device; src == dst -> QSIM_ERR_INVALID_ARGUMENT).  dst takes src's qubit layout.
+ * A mask bit >= n -> QSIM_ERR_OUT_OF_RANGE.  Synchronises. */
+int qsim_state_apply_pauli_sum(qsim_state* src, qsim_state* dst, const qsim_pauli_term* terms, size_t count);
+/* out[0] + i out[1] = <a|b>, both read in one common layout (their own when the two layouts are
+ * equal, else both are restored to the identity first); a == b gives the norm.  Partial sums are
+ * added in a fixed order: bitwise reproducible.  Synchronises. */
+int qsim_state_inner_product(qsim_state* a, qsim_state* b, double out[2]);
+/* Host-only: the inverse of one gate (self-inverse types unchanged, S <-> Sdag, T <-> Tdag,
+ * rotations with the angle negated).  An unknown type -> QSIM_ERR_RUNTIME. */
+int qsim_gate_inverse(const qsim_gate* g, qsim_gate* out);
+/* Host-only: what qsim_state_gradient would do for this circuit and observable: the parameterised
+ * gates (Rx, Ry, Rz, CRY, CRZ), the runs of non-parameterised gates the backward sweep inverts
+ * (those after the first parameterised gate; the gates before it are never undone), and the
+ * passes over the state of the Pauli-sum apply.  Errors as qsim_state_gradient. */
+int qsim_gradient_plan(int n_qubits, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms,
+                       size_t nterms, int* n_params, int* n_segments, int* apply_passes);
+/* The state holds |psi0> (whatever it holds now).  Runs the circuit as qsim_run(s, gates, count,
+ * flags) would, then *value = <psi|H|psi> and grad[k] = dE/d(parameter of gate k) for k < count
+ * (0.0 for a gate without a parameter), by the adjoint method: one backward sweep over two 2^n
+ * work states (a copy of the state and H times it), one pass over both per parameterised gate,
+ * instead of the two circuit runs per parameter of a parameter shift.  After the
+ * call the state holds U|psi0> exactly as qsim_run alone leaves it (amplitudes, qubit layout,
+ * relayout buffer); the sweep never writes to it.  The work states stay on the state between
+ * calls (counted by qsim_state_memory_bytes) until qsim_state_gradient_release or
+ * qsim_state_destroy; if they cannot be allocated: QSIM_ERR_DEVICE, the state holding U|psi0>.
+ * A parameterised step is one fused launch (bra-ket + U^dagger of both work states);
+ * QSIM_ADJOINT_FUSED=0 (read at every call) composes it from a reduction and two per-gate
+ * launches.  Runs of other gates are inverted as fused passes or per gate, as flags says.
+ * count == 0: *value = <H> of the state as it is; nterms == 0: *value = 0, all-zero gradient, no
+ * sweep.  Null pointers -> QSIM_ERR_INVALID_ARGUMENT, a mask bit >= n -> QSIM_ERR_OUT_OF_RANGE,
+ * a bad gate -> the code of qsim_run.  Bitwise reproducible.  Synchronises. */
+int qsim_state_gradient(qsim_state* s, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms,
+                        size_t nterms, int flags, double* value, double* grad);
+int qsim_state_gradient_release(qsim_state* s); /* free the gradient work buffers now */
+
 /* ---- timing (bench / profiling) ---- */
 /* Enable per-launch HIP-event timing on the state's stream; kernels are attributed by name. */
 int qsim_state_profile(qsim_state* s, int enable);

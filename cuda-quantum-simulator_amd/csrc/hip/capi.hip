@@ -196,6 +196,22 @@ struct GradWork {
     }
 };
 
+// Run sharing (engine.hpp SharePlan; the contract: include/qsim_hip.h qsim_set_run_share): the
+// joint plan of `copies` runs of one circuit, its compiled kernels, and how far the current cycle
+// has come.  armed: the state lies in one of the joint plan's layouts and identical fused runs are
+// executed as calls of the cycle; calls > 0: gates may be pending (share_flush).
+struct ShareState {
+    std::vector<qsim_gate> gates;  // the circuit sp was planned for
+    SharePlan sp;
+    JitState jit;
+    bool have = false;     // sp holds a joint plan for `gates`
+    bool refused = false;  // no joint plan pays for `gates`: never tried again
+    bool armed = false;
+    bool completed = false;  // a whole cycle has run since the state was armed
+    int calls = 0;         // calls of the current cycle so far
+    size_t next = 0;       // the first joint pass not yet launched
+};
+
 struct qsim_state {
     int n = 0;
     int device = 0;
@@ -239,6 +255,15 @@ struct qsim_state {
     hipStream_t noise_stream = nullptr;
     hipEvent_t nev_map[2] = {}, nev_pull[2] = {}, nev_start = nullptr;
     std::unique_ptr<GradWork> grad;  // adjoint gradients: work states and plans (null until used)
+    // run sharing: the gate list of the last fused qsim_run (cleared by every reader and writer of
+    // amplitudes in between), the cycle, and share_block (a caller that reads right after its run)
+    std::vector<qsim_gate> last_gates;
+    std::unique_ptr<ShareState> share;
+    bool share_block = false;
+    // back-off: cycles in a row that a reader ended before one whole cycle had run, and the
+    // identical repeats to let pass unshared before arming again (2^strikes - 1, at most 63) — a
+    // loop of "run twice, read" must not pay the arming (a gate-free pass, a flush plan) each time
+    int share_strikes = 0, share_wait = 0;
     ~qsim_state() {
         if (stream) (void)hipStreamSynchronize(stream);
         grad.reset();
@@ -417,8 +442,12 @@ static void trim_noise_buffers(qsim_state* s) {
 }
 
 // One fused plan on the state: relayout passes alternate between the state's two buffers.
-static void launch_plan(qsim_state* s, const Plan& plan, Timer* tm, const JitModule* jm) {
+// [first, last): the passes to launch (run sharing launches a joint plan piecewise).
+static void launch_plan(qsim_state* s, const Plan& plan, Timer* tm, const JitModule* jm, size_t first = 0,
+                        size_t last = SIZE_MAX) {
     FusedRange range;
+    range.first = first;
+    range.last = last;
     bool relayout = false;
     for (const FusedPass& p : plan.passes) relayout = relayout || p.relayout;
     if (relayout) {
@@ -452,10 +481,139 @@ static void run_fused(qsim_state* s, const std::vector<Op>& ops, bool jit = true
         for (hipFunction_t f : jm->fn) s->last_jit_passes += f != nullptr;
 }
 
+// ---- run sharing ----
+static qsim_gate map_gate(const qsim_state* s, const qsim_gate& g);
+static bool same_gates(const std::vector<qsim_gate>& a, const qsim_gate* b, size_t nb) {
+    if (a.size() != nb || nb == 0) return false;
+    for (size_t i = 0; i < nb; ++i) {
+        const qsim_gate &x = a[i], &y = b[i];
+        if (x.type != y.type || x.nqubits != y.nqubits || x.parameter != y.parameter) return false;
+        for (int j = 0; j < x.nqubits && j < 3; ++j)
+            if (x.qubits[j] != y.qubits[j]) return false;
+    }
+    return true;
+}
+// Pending gates are dropped (the amplitudes are about to be overwritten, or the state destroyed).
+static void share_discard(qsim_state* s) {
+    s->last_gates.clear();
+    if (!s->share) return;
+    s->share->armed = false;
+    s->share->calls = 0;
+    s->share->next = 0;
+}
+// Before anything but the next identical fused run touches the amplitudes: the requested gates
+// of the cycle that no launched pass held, lowered under the layout the state is in and run in
+// circuit order as an ordinary fused plan.  Ends the cycle (its plan stays for the next one).
+static void share_flush(qsim_state* s) {
+    s->last_gates.clear();
+    if (!s->share || !s->share->armed) return;
+    ShareState& sh = *s->share;
+    const int calls = sh.calls;
+    const size_t next = sh.next;
+    if (sh.completed) {
+        s->share_strikes = 0;
+    } else {
+        s->share_strikes = std::min(6, s->share_strikes + 1);
+        s->share_wait = (1 << s->share_strikes) - 1;
+    }
+    sh.armed = false;
+    sh.calls = 0;
+    sh.next = 0;
+    if (calls == 0) return;
+    std::vector<Op> ops;
+    for (int g : share_pending(sh.sp, next, calls)) {
+        ops.push_back(lower_gate(map_gate(s, sh.gates[(size_t)g % sh.sp.count]), s->n));
+        ops.back().src = (int)ops.size() - 1;
+    }
+    if (ops.empty()) return;
+    const int th = s->tile_h >= 0 ? s->tile_h : tile_height_for(s->n);
+    const TileHeightScope tile_h(th, tile_rb_for(s->n, th));
+    const int passes = s->last_passes, jit_passes = s->last_jit_passes;
+    run_fused(s, ops);
+    s->last_passes = passes;  // (qsim_state_last_run keeps describing the last qsim_run call)
+    s->last_jit_passes = jit_passes;
+}
+// A fused run has just executed the gate list of the fused run before it: plan `copies` of it as
+// one relayout plan (once per circuit), bring the state to that plan's first layout with one
+// gate-free pass and arm the cycle; the next identical runs are its calls (share_call).
+static void share_arm_impl(qsim_state* s, const qsim_gate* gates, size_t count);
+static void share_arm(qsim_state* s, const qsim_gate* gates, size_t count) {
+    if (s->share_wait > 0) {  // (back-off after cycles that readers cut short)
+        --s->share_wait;
+        return;
+    }
+    // The run's own plan has been launched already: a failure here (planning, the compile, the
+    // gate-free pass's launch) must not fail the run — the state stays unarmed and runs unshared.
+    try {
+        share_arm_impl(s, gates, count);
+    } catch (const std::exception&) {
+        (void)hipGetLastError();
+        if (s->share) {
+            s->share->armed = false;
+            s->share->have = false;
+            s->share->refused = true;  // (not tried again for this circuit on this state)
+        }
+    }
+}
+static void share_arm_impl(qsim_state* s, const qsim_gate* gates, size_t count) {
+    const int n = s->n;
+    if (s->pinned || s->share_block || !run_share_enabled(n) || !relabel_mode_on() || tile_height_is_set()) return;
+    if (!s->share) s->share = std::make_unique<ShareState>();
+    const int copies = run_share_copies();
+    if (!(s->share->have || s->share->refused) || !same_gates(s->share->gates, gates, count) ||
+        (s->share->have && s->share->sp.copies != copies)) {
+        if (s->share->jit.mod) QSIM_HIPCHK(hipStreamSynchronize(s->stream));  // its kernels may be queued
+        s->share = std::make_unique<ShareState>();
+        ShareState& sh = *s->share;
+        sh.gates.assign(gates, gates + count);
+        sh.have = plan_share(n, gates, count, copies, (size_t)std::max(1, s->last_passes), sh.sp);
+        sh.refused = !sh.have;
+    }
+    ShareState& sh = *s->share;
+    if (!sh.have || !ensure_alt(s)) return;
+    const TileHeightScope scope(6, tile_rb_for(n, 6));
+    // (inline compilation compiles the joint plan's kernels here, not in the cycle's first call)
+    (void)jit_for(sh.jit, sh.sp.plan, n);
+    if (s->perm != sh.sp.layouts[0]) {
+        const Plan move = plan_permutation_pass(n, s->perm, sh.sp.layouts[0]);
+        s->stages.upload(move.stages.data(), move.stages.size() * sizeof(Stage), s->stream);
+        launch_plan(s, move, &s->timer, nullptr);
+        s->perm = sh.sp.layouts[0];
+    }
+    s->relayout = true;  // (the state keeps its second buffer)
+    sh.armed = true;
+    sh.completed = false;
+    sh.calls = 0;
+    sh.next = 0;
+}
+// One call of the armed cycle: the longest prefix of not-yet-launched joint passes whose gates
+// all belong to the copies requested so far.
+static void share_call(qsim_state* s) {
+    ShareState& sh = *s->share;
+    const TileHeightScope scope(6, tile_rb_for(s->n, 6));
+    const Plan& plan = sh.sp.plan;
+    const JitModule* jm = jit_for(sh.jit, plan, s->n);
+    s->ops.upload(plan.ops.data(), plan.ops.size() * sizeof(TileOp), s->stream);
+    s->stages.upload(plan.stages.data(), plan.stages.size() * sizeof(Stage), s->stream);
+    size_t first = 0, last = 0, next = sh.next;
+    int calls = sh.calls;
+    const bool done = share_advance(sh.sp, calls, next, first, last);
+    if (last > first) launch_plan(s, plan, &s->timer, jm, first, last);
+    sh.calls = calls;  // (only now: a failed launch leaves the bookkeeping where the state is)
+    sh.next = next;
+    sh.completed = sh.completed || done;
+    s->perm = sh.sp.layouts[done ? 0 : last];
+    s->basis = false;
+    s->last_passes = (int)(last - first);
+    s->last_jit_passes = 0;
+    for (size_t k = first; k < last && jm && k < jm->fn.size(); ++k) s->last_jit_passes += jm->fn[k] != nullptr;
+}
+
 // Undo the relabeling: a fused network of physical SWAPs that brings logical qubit q back to
 // position q (exact data movement), then the identity map.  Every entry that reads or writes
 // amplitudes by index calls this first.
 static void canonicalize(qsim_state* s) {
+    share_flush(s);
     if (s->perm.empty()) return;
     const int n = s->n;
     // One gate-free relayout pass (relayout.hip) from 16 qubits: every amplitude stored at its
@@ -497,6 +655,7 @@ static void canonicalize(qsim_state* s) {
 }
 // Before an entry that overwrites every amplitude: the labels are dropped, not restored.
 static void drop_layout(qsim_state* s) {
+    share_discard(s);  // (pending gates of a run-sharing cycle: overwritten with the rest)
     if (s->relayout) {  // (a relayout plan's second buffer: as canonicalize would leave it)
         canonicalize(s);
     }
@@ -1043,6 +1202,7 @@ int qsim_state_init_zero(qsim_state* s) {
     return guarded([&] {
         check_state(s);
         DeviceGuard g(s->device);
+        share_discard(s);
         launch_init_basis(s->d, s->n, 1, 0, s->stream);
         QSIM_HIPCHK(hipStreamSynchronize(s->stream));
         s->perm.clear();
@@ -1059,6 +1219,7 @@ int qsim_state_init_basis(qsim_state* s, uint64_t idx) {
         check_state(s);
         if (idx >= (1ull << s->n)) fail(QSIM_ERR_INVALID_ARGUMENT, "Basis index out of range");
         DeviceGuard g(s->device);
+        share_discard(s);
         launch_init_basis(s->d, s->n, 1, idx, s->stream);
         QSIM_HIPCHK(hipStreamSynchronize(s->stream));
         s->perm.clear();
@@ -1083,6 +1244,7 @@ int qsim_apply_gate(qsim_state* s, const qsim_gate* g) {
         QSIM_REQUIRE(g, QSIM_ERR_INVALID_ARGUMENT, "null gate");
         DeviceGuard dg(s->device);
         validate_gate(*g, s->n);
+        share_flush(s);
         const Op op = lower_gate(map_gate(s, *g), s->n);
         s->basis = false;
         launch_op(s->d, s->n, 1, op, s->stream, &s->timer);
@@ -1095,6 +1257,17 @@ int qsim_run(qsim_state* s, const qsim_gate* gates, size_t count, int flags) {
         QSIM_REQUIRE(gates || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gate list");
         DeviceGuard dg(s->device);
         for (size_t i = 0; i < count; ++i) validate_gate(gates[i], s->n);
+        const bool fused = (flags & QSIM_RUN_FUSED) != 0;
+        if (s->share && s->share->armed) {
+            // the armed cycle's circuit again: its next call; anything else flushes first
+            if (fused && !s->share_block && same_gates(s->share->gates, gates, count)) {
+                share_call(s);
+                return;
+            }
+            share_flush(s);
+        }
+        // the gate list of the fused run before this one, with no reader or writer in between?
+        const bool repeat = fused && same_gates(s->last_gates, gates, count);
         auto lower_all = [&]() {
             std::vector<Op> ops;
             ops.reserve(count);
@@ -1125,9 +1298,12 @@ int qsim_run(qsim_state* s, const qsim_gate* gates, size_t count, int flags) {
         const TileHeightScope tile_h(th, tile_rb_for(s->n, th));  // plans of this run
         const std::vector<Op> ops = lower_all();
         s->basis = false;
-        if (flags & QSIM_RUN_FUSED) {
+        if (fused) {
             run_fused(s, ops);
+            if (!repeat) s->last_gates.assign(gates, gates + count);
+            else share_arm(s, gates, count);
         } else {
+            s->last_gates.clear();
             for (const Op& op : ops) launch_op(s->d, s->n, 1, op, s->stream, &s->timer);
         }
     });
@@ -1457,6 +1633,7 @@ int qsim_state_from_host(qsim_state* s, const double* src) {
         check_state(s);
         QSIM_REQUIRE(src, QSIM_ERR_INVALID_ARGUMENT, "null source");
         DeviceGuard dg(s->device);
+        share_discard(s);
         s->perm.clear();  // overwritten in logical order
         s->basis = false;
         QSIM_HIPCHK(hipMemcpyAsync(s->d, src, sizeof(double2) << s->n, hipMemcpyHostToDevice,
@@ -1484,6 +1661,7 @@ int qsim_state_total_probability(qsim_state* s, double* out) {
         check_state(s);
         QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
         DeviceGuard dg(s->device);
+        share_flush(s);
         *out = reduce_norm(s->d, s->n, -1, s->d_partials, s->d_result, s->stream);
     });
 }
@@ -1505,10 +1683,11 @@ int qsim_state_expectation(qsim_state* s, const qsim_pauli_term* terms, size_t c
         check_state(s);
         QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
         QSIM_REQUIRE(terms || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        DeviceGuard dg(s->device);
+        share_flush(s);  // (pending gates of a run-sharing cycle; the layout may change with them)
         const ExpectPlan plan = lower_expectation(s->n, terms, count, s->perm.empty() ? nullptr : s->perm.data());
         *out = 0.0;
         if (plan.terms.empty()) return;
-        DeviceGuard dg(s->device);
         launch_expectation(s->d, s->n, 1, plan, s->expect_terms, s->d_partials, s->d_result, s->stream, &s->timer);
         QSIM_HIPCHK(hipMemcpyAsync(out, s->d_result, sizeof(double), hipMemcpyDeviceToHost, s->stream));
         QSIM_HIPCHK(hipStreamSynchronize(s->stream));
@@ -1659,6 +1838,7 @@ int qsim_state_apply_pauli_sum(qsim_state* src, qsim_state* dst, const qsim_paul
         if (src->n != dst->n) fail(QSIM_ERR_INVALID_ARGUMENT, "states have different qubit counts");
         if (src->device != dst->device) fail(QSIM_ERR_INVALID_ARGUMENT, "states live on different devices");
         DeviceGuard dg(src->device);
+        share_flush(src);
         // (a handed-out device pointer always sees the identity layout)
         if (dst->pinned) prep(src, false);
         const ExpectPlan plan =
@@ -1679,6 +1859,8 @@ int qsim_state_inner_product(qsim_state* a, qsim_state* b, double out[2]) {
         if (a->n != b->n) fail(QSIM_ERR_INVALID_ARGUMENT, "states have different qubit counts");
         if (a->device != b->device) fail(QSIM_ERR_INVALID_ARGUMENT, "states live on different devices");
         DeviceGuard dg(a->device);
+        share_flush(a);
+        share_flush(b);
         if (a->perm != b->perm) {  // one common layout: the identity
             prep(a, false);
             prep(b, false);
@@ -1708,8 +1890,16 @@ int qsim_state_gradient(qsim_state* s, const qsim_gate* gates, size_t count, con
         QSIM_REQUIRE(value, QSIM_ERR_INVALID_ARGUMENT, "null value");
         QSIM_REQUIRE(grad || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gradient");
         check_gradient_args(s->n, gates, count, terms, nterms);
+        DeviceGuard dg(s->device);
+        share_flush(s);
     });
     if (rc != QSIM_OK) return rc;
+    // (the sweep below reads the state this run leaves: it runs its own plan whole)
+    struct ShareBlock {
+        qsim_state* s;
+        explicit ShareBlock(qsim_state* st) : s(st) { s->share_block = true; }
+        ~ShareBlock() { s->share_block = false; }
+    } share_block(s);
     // The forward run is qsim_run itself: the state ends exactly as a plain run leaves it, and
     // nothing below writes to it.
     if (count > 0 && (rc = qsim_run(s, gates, count, flags)) != QSIM_OK) return rc;
@@ -1968,6 +2158,7 @@ int qsim_dm_run(qsim_state* s, int n, const qsim_gate* gates, size_t count,
         QSIM_REQUIRE(gates || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gate list");
         QSIM_REQUIRE(channels || n_channels == 0, QSIM_ERR_INVALID_ARGUMENT, "null channel list");
         DeviceGuard dg(s->device);
+        share_flush(s);
         std::vector<Op> ops;
         dm_lower(n, gates, count, channels, n_channels, ops, (flags & QSIM_DM_REFERENCE_Y) != 0);
         // the state-vector size rule for the 2n index bits (13-qubit tiles for 26-28 bits: DM 13-14

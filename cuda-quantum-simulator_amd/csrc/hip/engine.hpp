@@ -221,18 +221,52 @@ struct RelayoutChoice {
     std::vector<Op> ops;    // the circuit lowered under perm
     Plan plan;
     double cost_us = 0.0;   // predicted (layout model)
+    // layouts[k] (logical -> physical) is what pass k loads and pass k - 1 stores; layouts[K] =
+    // layouts[0] = perm.  pass_src[k]: the circuit gates (Op::src) pass k applies.
+    std::vector<std::vector<int>> layouts;
+    std::vector<std::vector<int>> pass_src;
 };
 bool plan_relayout(int n, const std::function<std::vector<Op>(const std::vector<int>&)>& lower,
                    size_t max_passes, RelayoutChoice& out);
 // Up to QSIM_RELAYOUT_VARIANTS (default 3) closed tile sequences of the fewest passes, each with
 // QSIM_RELAYOUT_LAYOUT_VARIANTS (default 2) position choices: relayout choices, best predicted first — the candidates a timed first run compares; memoised.
+// period > 0 (run sharing): the circuit is copies of `period` gates each, and no pass holds a gate
+// more than one copy past its oldest gate's.
 size_t plan_relayout_variants(int n, const std::function<std::vector<Op>(const std::vector<int>&)>& lower,
-                              size_t max_passes, std::vector<RelayoutChoice>& out);
+                              size_t max_passes, std::vector<RelayoutChoice>& out, size_t period = 0);
 bool relayout_enabled(int n);  // QSIM_RELAYOUT (default 1), QSIM_RELAYOUT_MIN_QUBITS (default 20)
 void relayout_configure(int mode, int min_qubits);  // qsim_set_relayout; < 0 leaves a setting
 // A single gate-free relayout pass taking logical qubit q from physical perm[q] to q (n >= 12).
 Plan plan_permutation_pass(int n, const std::vector<int>& perm);
+// The same pass between any two layouts: logical qubit q goes from physical from[q] to to[q]
+// (either may be empty: the identity).
+Plan plan_permutation_pass(int n, const std::vector<int>& from, const std::vector<int>& to);
 bool relayout_forced();  // mode 2: a relayout plan whenever one exists (tests)
+// Run sharing (relayout.hip; driven by capi.hip qsim_run): `copies` consecutive runs of one
+// circuit planned as ONE relayout plan and executed piecewise, call by call.  Call j of a cycle
+// launches the longest prefix of not-yet-launched passes whose gates all belong to copies <= j;
+// the requested gates in later passes stay pending until the next call or the next reader.
+struct SharePlan {
+    int copies = 0;
+    size_t count = 0;                        // gates per copy
+    std::vector<Op> ops;                     // the copies in order, lowered under layouts[0]
+    Plan plan;
+    std::vector<std::vector<int>> layouts;   // RelayoutChoice::layouts of the joint plan
+    std::vector<std::vector<int>> pass_src;  // joint gate indices (copy * count + gate) per pass
+    std::vector<int> pass_copy;              // the highest copy a pass holds a gate of (-1: none)
+};
+// False when no joint plan needs fewer than copies * single_passes passes (memoised per circuit,
+// in process and on disk, apart from single-run layout decisions: memo kind 4).
+bool plan_share(int n, const qsim_gate* gates, size_t count, int copies, size_t single_passes, SharePlan& out);
+// One more call of a cycle (calls: requested so far, next: the first pass not yet launched; both
+// advanced): the passes [first, last) it launches.  True when the cycle is complete: every pass
+// has run, nothing is pending, and calls / next are back at 0.
+bool share_advance(const SharePlan& sp, int& calls, size_t& next, size_t& first, size_t& last);
+// Requested gates (joint indices below calls * count) in passes >= next_pass, in circuit order.
+std::vector<int> share_pending(const SharePlan& sp, size_t next_pass, int calls);
+bool run_share_enabled(int n);  // QSIM_RUN_SHARE (default 1), from the relayout size threshold
+int run_share_copies();         // QSIM_RUN_SHARE_COPIES (default 4)
+void run_share_configure(int mode, int copies);  // qsim_set_run_share; negative: unchanged
 int tile_height_default();             // the h that hmax < 0 means (scope, setting, env, 6)
 int tile_height_for(int n);            // a single-GPU state's height (the setting, or by size)
 bool tile_height_is_set();             // qsim_set_tile_height or QSIM_TILE_HMAX in force

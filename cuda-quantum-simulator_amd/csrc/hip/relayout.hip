@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <mutex>
 #include <random>
 #include <unordered_set>
@@ -66,15 +67,30 @@ struct Search {
     int n;
     const std::vector<uint64_t>& need;  // the qubits the tile must hold
     size_t window = 512;
+    // Run sharing (plan_share): the gates are copies of one circuit of `period` gates.  A pass
+    // whose oldest remaining gate belongs to copy c holds gates of copy c only while more than
+    // `tail` gates of that copy remain, and of copies c and c + 1 after that — else the planner
+    // hoists gates of every later copy into the first passes (a qubit whose gates all lie in one
+    // tile), and no pass could be launched before the last copy is requested; and with c + 1
+    // allowed from the start, none before the second.  0: no limit.
+    size_t period = 0, tail = 0;
+    // the first copy no gate of a pass over `rem` may come from
+    size_t copy_limit(const std::vector<int>& rem) const {
+        if (period == 0) return SIZE_MAX;
+        const size_t c = (size_t)rem[0] / period;
+        const size_t left = std::lower_bound(rem.begin(), rem.end(), (int)((c + 1) * period)) - rem.begin();
+        return left > tail ? c + 1 : c + 2;
+    }
 
     // (gates admitted, gates partly covered) over the first `window` remaining gates
     int score(const std::vector<int>& rem, uint64_t allowed) const {
         uint64_t blocked = 0;
         int full = 0, part = 0;
         const size_t m = std::min(rem.size(), window);
+        const size_t lim = copy_limit(rem) * std::max<size_t>(period, 1);
         for (size_t i = 0; i < m; ++i) {
             const uint64_t q = qm[rem[i]], nd = need[rem[i]];
-            if (q & blocked) {
+            if ((q & blocked) || (period && (size_t)rem[i] >= lim)) {
                 blocked |= q;
             } else if ((nd & ~allowed) == 0) {
                 ++full;
@@ -90,9 +106,10 @@ struct Search {
     std::vector<int> apply(const std::vector<int>& rem, uint64_t allowed, std::vector<int>* ran = nullptr) const {
         std::vector<int> out;
         uint64_t blocked = 0;
+        const size_t lim = rem.empty() ? 0 : copy_limit(rem) * std::max<size_t>(period, 1);
         for (int i : rem) {
             const uint64_t q = qm[i];
-            if ((q & blocked) == 0 && (need[i] & ~allowed) == 0) {
+            if ((q & blocked) == 0 && (need[i] & ~allowed) == 0 && !(period && (size_t)i >= lim)) {
                 if (ran) ran->push_back(i);
                 continue;
             }
@@ -330,6 +347,7 @@ uint64_t choose_run(uint64_t pool, const int* uses) {
 
 }  // namespace
 
+static int share_tail_percent();
 static std::atomic<int> g_relayout{-1}, g_relayout_min{-1};
 bool relayout_enabled(int n) {
     if (g_relayout.load() < 0) g_relayout.store(env_int("QSIM_RELAYOUT", 1));
@@ -429,6 +447,10 @@ bool build_choice(int n, const std::function<std::vector<Op>(const std::vector<i
     }
     out.plan = std::move(plan);
     out.cost_us = cost;
+    out.layouts = std::move(L);
+    out.pass_src.assign(K, {});
+    for (size_t k = 0; k < K; ++k)
+        for (int i : ran[k]) out.pass_src[k].push_back(logical[i].src);
     return true;
 }
 
@@ -459,14 +481,15 @@ std::vector<unsigned char> ops_key(const std::vector<Op>& ops) {
 }  // namespace
 
 size_t plan_relayout_variants(int n, const std::function<std::vector<Op>(const std::vector<int>&)>& lower,
-                              size_t max_passes, std::vector<RelayoutChoice>& out) {
+                              size_t max_passes, std::vector<RelayoutChoice>& out, size_t period) {
     out.clear();
     if (n < kTile + kRun || n - kTile > 32) return 0;
     std::vector<int> id(n);
     for (int q = 0; q < n; ++q) id[q] = q;
     const std::vector<Op> logical = lower(id);
     if (logical.empty()) return 0;
-    const std::vector<unsigned char> key = ops_key(logical);
+    std::vector<unsigned char> key = ops_key(logical);
+    for (int b = 0; b < 8; ++b) key.push_back((unsigned char)(period >> (8 * b)));
     {
         std::lock_guard<std::mutex> l(g_rl_mu);
         for (RelayoutMemo& m : g_rl_memo)
@@ -484,7 +507,9 @@ size_t plan_relayout_variants(int n, const std::function<std::vector<Op>(const s
         fits = fits && __builtin_popcountll(nd[i]) <= kTile - kRun;
     }
     if (fits) {
-        const Search S{qm, n, nd};
+        Search S{qm, n, nd};
+        S.period = period;
+        S.tail = period * (size_t)share_tail_percent() / 100;
         static const int width = env_int("QSIM_RELAYOUT_BEAM", 96);
         static const int nvar = std::max(1, env_int("QSIM_RELAYOUT_VARIANTS", 3));
         static const int nlay = std::max(1, env_int("QSIM_RELAYOUT_LAYOUT_VARIANTS", 2));
@@ -550,6 +575,129 @@ Plan plan_permutation_pass(int n, const std::vector<int>& perm) {
     return plan;
 }
 
+// Between two layouts: name every qubit by its position under `to` — the qubit named x sits at
+// from[to^-1[x]] and goes to position x, which is the pass above.
+Plan plan_permutation_pass(int n, const std::vector<int>& from, const std::vector<int>& to) {
+    if ((!from.empty() && (int)from.size() != n) || (!to.empty() && (int)to.size() != n))
+        fail(QSIM_ERR_RUNTIME, "permutation pass: layout of another size");
+    std::vector<int> rel(n);
+    for (int q = 0; q < n; ++q) rel[to.empty() ? q : to[q]] = from.empty() ? q : from[q];
+    return plan_permutation_pass(n, rel);
+}
+
+// ---------------------------------------------------------------------------------------
+// Run sharing: the joint plan of `copies` runs of one circuit and its piecewise bookkeeping.
+// ---------------------------------------------------------------------------------------
+static std::atomic<int> g_share{-1}, g_share_copies{-1};
+static void share_defaults() {
+    if (g_share.load() < 0) g_share.store(env_int("QSIM_RUN_SHARE", 1) != 0 ? 1 : 0);
+    if (g_share_copies.load() < 0) g_share_copies.store(std::min(16, std::max(2, env_int("QSIM_RUN_SHARE_COPIES", 4))));
+}
+bool run_share_enabled(int n) {
+    share_defaults();
+    return g_share.load() != 0 && relayout_enabled(n);
+}
+int run_share_copies() {
+    share_defaults();
+    return g_share_copies.load();
+}
+void run_share_configure(int mode, int copies) {
+    share_defaults();
+    if (mode >= 0) g_share.store(mode != 0 ? 1 : 0);
+    if (copies >= 0) g_share_copies.store(std::min(16, std::max(2, copies)));
+}
+
+// QSIM_RUN_SHARE_TAIL (per cent, default 50; include/qsim_hip.h qsim_set_run_share): the share of
+// a copy's gates that must have run before a pass may also take gates of the next copy.
+static int share_tail_percent() {
+    static const int v = std::min(100, std::max(0, env_int("QSIM_RUN_SHARE_TAIL", 50)));
+    return v;
+}
+
+bool plan_share(int n, const qsim_gate* gates, size_t count, int copies, size_t single_passes, SharePlan& out) {
+    if (copies < 2 || count == 0 || single_passes == 0) return false;
+    const TileHeightScope scope(6, tile_rb_for(n, 6));
+    // memo key (kind 4: never read as a single-run decision): everything the answer depends on —
+    // the gates' meaningful fields (no padding, no unused qubit slots), the number of copies, the
+    // single plan's pass count the joint plan is compared with, and the hoisting limit
+    std::vector<unsigned char> key;
+    auto put = [&](const void* p, size_t b) {
+        const unsigned char* c = static_cast<const unsigned char*>(p);
+        key.insert(key.end(), c, c + b);
+    };
+    for (size_t i = 0; i < count; ++i) {
+        const int32_t f[5] = {gates[i].type, gates[i].nqubits, gates[i].nqubits > 0 ? gates[i].qubits[0] : -1,
+                              gates[i].nqubits > 1 ? gates[i].qubits[1] : -1,
+                              gates[i].nqubits > 2 ? gates[i].qubits[2] : -1};
+        put(f, sizeof f);
+        put(&gates[i].parameter, sizeof(double));
+    }
+    const int64_t tailkey[3] = {copies, (int64_t)single_passes, share_tail_percent()};
+    put(tailkey, sizeof tailkey);
+    std::vector<int> memo;
+    const bool have_memo = layout_memo_get(n, 4, key.data(), key.size(), memo);
+    if (have_memo && memo.empty()) return false;  // decided before: no cycle pays for this circuit
+    const size_t total = count * (size_t)copies;
+    auto lower = [&](const std::vector<int>& pi) {  // the copies in order, as runSequence lowers them
+        std::vector<Op> ops;
+        ops.reserve(total);
+        for (size_t i = 0; i < total; ++i) {
+            qsim_gate g = gates[i % count];
+            for (int j = 0; j < g.nqubits && j < 3; ++j) g.qubits[j] = pi[g.qubits[j]];
+            ops.push_back(lower_gate(g, n));
+            ops.back().src = (int)i;
+        }
+        return ops;
+    };
+    std::vector<RelayoutChoice> vs;
+    plan_relayout_variants(n, lower, SIZE_MAX, vs, count);
+    RelayoutChoice* rc = nullptr;
+    for (RelayoutChoice& v : vs)
+        if (have_memo && v.perm == memo) rc = &v;
+    if (!rc && !vs.empty()) rc = &vs.front();  // the best predicted variant
+    if (!rc || rc->plan.passes.size() >= (size_t)copies * single_passes) {
+        if (!have_memo) layout_memo_put(n, 4, key.data(), key.size(), {});
+        return false;
+    }
+    if (!have_memo) layout_memo_put(n, 4, key.data(), key.size(), rc->perm);
+    out.copies = copies;
+    out.count = count;
+    out.ops = std::move(rc->ops);
+    out.plan = std::move(rc->plan);
+    out.layouts = std::move(rc->layouts);
+    out.pass_src = std::move(rc->pass_src);
+    out.pass_copy.clear();
+    for (const std::vector<int>& src : out.pass_src) {
+        int c = -1;
+        for (int g : src) c = std::max(c, (int)((size_t)g / count));
+        out.pass_copy.push_back(c);
+    }
+    return true;
+}
+
+bool share_advance(const SharePlan& sp, int& calls, size_t& next, size_t& first, size_t& last) {
+    ++calls;
+    first = next;
+    last = first;
+    while (last < sp.pass_copy.size() && sp.pass_copy[last] < calls) ++last;
+    next = last;
+    if (calls < sp.copies) return false;
+    if (next != sp.pass_copy.size()) fail(QSIM_ERR_RUNTIME, "run sharing: passes left after the last call of a cycle");
+    calls = 0;
+    next = 0;
+    return true;
+}
+
+std::vector<int> share_pending(const SharePlan& sp, size_t next_pass, int calls) {
+    std::vector<int> out;
+    const size_t lim = (size_t)calls * sp.count;
+    for (size_t k = next_pass; k < sp.pass_src.size(); ++k)
+        for (int g : sp.pass_src[k])
+            if ((size_t)g < lim) out.push_back(g);
+    std::sort(out.begin(), out.end());
+    return out;
+}
+
 // ---------------------------------------------------------------------------------------
 // Host execution of a plan (tests: qsim_plan_exec_host).  Every staged pass is run tile by
 // tile exactly as k_fused_staged / the generated kernels address it — first-stage HBM offsets,
@@ -605,8 +753,9 @@ void exec_stage_op(const TileOp& op, cd* v, int R, uint32_t jb) {
     }
 }
 
-void exec_plan_host(const Plan& plan, int n, std::vector<cd>& st) {
-    for (const FusedPass& p : plan.passes) {
+void exec_plan_host(const Plan& plan, int n, std::vector<cd>& st, size_t first = 0, size_t last = SIZE_MAX) {
+    for (size_t pidx = first; pidx < std::min(last, plan.passes.size()); ++pidx) {
+        const FusedPass& p = plan.passes[pidx];
         if (p.single >= 0 || p.h < 4) fail(QSIM_ERR_RUNTIME, "host execution covers staged passes only");
         const int tb = 6 + p.h, RB = p.rb, R = 1 << RB, nthr = (1 << tb) >> RB;
         const int r0 = p.r0, nh = tb - r0, lt = n - tb;
@@ -792,6 +941,152 @@ extern "C" int qsim_plan_relayout(int n_qubits, const qsim_gate* gates, size_t c
         set_last_error(e.what());
         return QSIM_ERR_RUNTIME;
     }
+}
+
+namespace qsim_hip {
+namespace {
+// The single-run plan the host view plays (the engine's is the first run's layout choice): the
+// circuit's relayout plan where relayout plans are on and one exists, else the fixed-layout plan
+// under the identity labels.
+void host_single_plan(int n, const qsim_gate* gates, size_t count, std::vector<int>& perm, Plan& plan) {
+    auto lower = [&](const std::vector<int>& pi) {
+        std::vector<Op> ops;
+        for (size_t i = 0; i < count; ++i) {
+            qsim_gate m = gates[i];
+            for (int j = 0; j < m.nqubits && j < 3; ++j) m.qubits[j] = pi[m.qubits[j]];
+            ops.push_back(lower_gate(m, n));
+            ops.back().src = (int)i;
+        }
+        return ops;
+    };
+    const TileHeightScope scope(6, tile_rb_for(n, 6));
+    perm.resize(n);
+    for (int q = 0; q < n; ++q) perm[q] = q;
+    RelayoutChoice rc;
+    if (relayout_enabled(n) && plan_relayout(n, lower, SIZE_MAX, rc)) {
+        perm = rc.perm;
+        plan = std::move(rc.plan);
+    } else {
+        plan = plan_fused(lower(perm), n, 6);
+    }
+}
+}  // namespace
+}  // namespace qsim_hip
+
+extern "C" int qsim_plan_share_host(int n_qubits, const qsim_gate* gates, size_t count, int copies, int calls,
+                                    double* amps, int32_t* passes_per_call, int32_t* pending_per_call) {
+    using namespace qsim_hip;
+    try {
+        if (n_qubits < 10 || n_qubits > 26) fail(QSIM_ERR_INVALID_ARGUMENT, "host execution: 10..26 qubits");
+        if (!amps || !gates || count == 0 || calls < 0) fail(QSIM_ERR_INVALID_ARGUMENT, "bad argument");
+        const int n = n_qubits;
+        for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n);
+        if (copies <= 0) copies = run_share_copies();
+        std::vector<int> cur;
+        Plan single;
+        host_single_plan(n, gates, count, cur, single);
+        const uint64_t N = 1ull << n;
+        auto physical = [&](uint64_t i) {
+            uint64_t k = 0;
+            for (int q = 0; q < n; ++q)
+                if ((i >> q) & 1ull) k |= 1ull << cur[q];
+            return k;
+        };
+        std::vector<cd> st(N);
+        for (uint64_t i = 0; i < N; ++i) st[physical(i)] = cd(amps[2 * i], amps[2 * i + 1]);
+        SharePlan sp;
+        bool armed = false, refused = false;
+        int cyc_calls = 0;
+        size_t next = 0;
+        for (int c = 0; c < calls; ++c) {
+            int launched = 0, pending = 0;
+            if (armed) {
+                size_t first = 0, last = 0;
+                const bool done = share_advance(sp, cyc_calls, next, first, last);
+                exec_plan_host(sp.plan, n, st, first, last);
+                launched = (int)(last - first);
+                cur = sp.layouts[done ? 0 : last];
+                pending = (int)share_pending(sp, next, cyc_calls).size();
+            } else {
+                exec_plan_host(single, n, st);
+                launched = (int)single.passes.size();
+                // the same gate list as the run before: arm a cycle (as qsim_run does)
+                if (c >= 1 && !refused && run_share_enabled(n)) {
+                    if (plan_share(n, gates, count, copies, single.passes.size(), sp)) {
+                        if (cur != sp.layouts[0]) {
+                            exec_plan_host(plan_permutation_pass(n, cur, sp.layouts[0]), n, st);
+                            cur = sp.layouts[0];
+                        }
+                        armed = true;
+                    } else {
+                        refused = true;
+                    }
+                }
+            }
+            if (passes_per_call) passes_per_call[c] = launched;
+            if (pending_per_call) pending_per_call[c] = pending;
+        }
+        if (armed && cyc_calls > 0) {  // flush: the pending gates under the current layout
+            std::vector<Op> ops;
+            for (int g : share_pending(sp, next, cyc_calls)) {
+                qsim_gate m = gates[(size_t)g % count];
+                for (int j = 0; j < m.nqubits && j < 3; ++j) m.qubits[j] = cur[m.qubits[j]];
+                ops.push_back(lower_gate(m, n));
+                ops.back().src = (int)ops.size() - 1;
+            }
+            if (!ops.empty()) {
+                const TileHeightScope scope(6, tile_rb_for(n, 6));
+                exec_plan_host(plan_fused(ops, n, 6), n, st);
+            }
+        }
+        for (uint64_t i = 0; i < N; ++i) {
+            const cd a = st[physical(i)];
+            amps[2 * i] = a.real();
+            amps[2 * i + 1] = a.imag();
+        }
+        return QSIM_OK;
+    } catch (const Error& e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return QSIM_ERR_RUNTIME;
+    }
+}
+
+extern "C" int qsim_plan_share_info(int n_qubits, const qsim_gate* gates, size_t count, int copies, int* joint_passes,
+                                    int* single_passes, int32_t* pass_copy, size_t cap) {
+    using namespace qsim_hip;
+    try {
+        if (n_qubits < 10 || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        if (!gates || count == 0) fail(QSIM_ERR_INVALID_ARGUMENT, "bad argument");
+        for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n_qubits);
+        if (copies <= 0) copies = run_share_copies();
+        std::vector<int> perm;
+        Plan single;
+        host_single_plan(n_qubits, gates, count, perm, single);
+        SharePlan sp;
+        const bool ok = plan_share(n_qubits, gates, count, copies, single.passes.size(), sp);
+        if (joint_passes) *joint_passes = ok ? (int)sp.plan.passes.size() : 0;
+        if (single_passes) *single_passes = (int)single.passes.size();
+        for (size_t k = 0; ok && pass_copy && k < cap && k < sp.pass_copy.size(); ++k) pass_copy[k] = sp.pass_copy[k];
+        return QSIM_OK;
+    } catch (const Error& e) {
+        set_last_error(e.what());
+        return e.code;
+    } catch (const std::exception& e) {
+        set_last_error(e.what());
+        return QSIM_ERR_RUNTIME;
+    }
+}
+
+extern "C" int qsim_set_run_share(int mode, int copies) {
+    if (mode > 1 || (copies >= 0 && copies < 2)) {
+        qsim_hip::set_last_error("run share: mode 0 or 1, at least 2 copies");
+        return QSIM_ERR_INVALID_ARGUMENT;
+    }
+    qsim_hip::run_share_configure(mode, copies);
+    return QSIM_OK;
 }
 
 extern "C" int qsim_set_relayout(int mode, int min_qubits) {

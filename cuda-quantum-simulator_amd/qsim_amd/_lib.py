@@ -111,6 +111,11 @@ _sig(hip, "qsim_plan_relayout", [c_int, POINTER(qsim_gate), c_size_t, POINTER(c_
                                  POINTER(c_double)])
 _sig(hip, "qsim_plan_exec_host", [c_int, POINTER(qsim_gate), c_size_t, c_int, _P, POINTER(c_int32),
                                   POINTER(c_int)])
+_sig(hip, "qsim_set_run_share", [c_int, c_int])
+_sig(hip, "qsim_plan_share_host", [c_int, POINTER(qsim_gate), c_size_t, c_int, c_int, _P, POINTER(c_int32),
+                                   POINTER(c_int32)])
+_sig(hip, "qsim_plan_share_info", [c_int, POINTER(qsim_gate), c_size_t, c_int, POINTER(c_int), POINTER(c_int),
+                                   POINTER(c_int32), c_size_t])
 _sig(hip, "qsim_set_calibrate", [c_int, c_int])
 _sig(hip, "qsim_set_tile_height", [c_int])
 _sig(hip, "qsim_set_tile_rb7", [c_int])

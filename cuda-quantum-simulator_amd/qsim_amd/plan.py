@@ -63,6 +63,14 @@ def set_relayout(mode: int = -1, min_qubits: int = -1) -> None:
     _lib.check(_lib.hip.qsim_set_relayout(mode, min_qubits))
 
 
+def set_run_share(mode: int = -1, copies: int = -1) -> None:
+    """Run sharing (qsim_set_run_share): repeated fused runs of one circuit executed as calls of
+    ONE joint relayout plan of `copies` runs (default 4); gates a call could not yet run stay
+    pending until the next call or the next reader of the state.  mode 0 off, 1 on (default, for
+    states from the relayout size threshold); negative arguments leave a setting unchanged."""
+    _lib.check(_lib.hip.qsim_set_run_share(mode, copies))
+
+
 def set_calibrate(mode: int = -1, min_qubits: int = -1) -> None:
     """Time the layout model's top candidates on the device at a basis state's first run and
     keep the fastest (qsim_set_calibrate; needs set_jit(2)): mode 0 off, 1 on."""
@@ -88,17 +96,19 @@ def set_tile_ctrl_out(mode: int = -1) -> None:
 
 
 # The shipped policy (include/qsim_hip.h; environment variables unset).
-DEFAULTS = {"jit": (1, 20), "relabel": (1, 26), "relayout": (1, 20), "calibrate": (1, 26)}
+DEFAULTS = {"jit": (1, 20), "relabel": (1, 26), "relayout": (1, 20), "calibrate": (1, 26),
+            "run_share": (1, 4)}
 
 
 def restore_defaults() -> None:
     """Put every process-wide planning policy back to the shipped defaults: background JIT from
     20 qubits, relabeling from 26, relayout plans from 20, calibrated first runs from 26 (with
-    inline compilation), the size rule for tile heights (tests call this after changing any)."""
+    inline compilation), run sharing on with 4 copies, the size rule for tile heights (tests call this after changing any)."""
     set_jit(*DEFAULTS["jit"])
     set_relabel(*DEFAULTS["relabel"])
     set_relayout(*DEFAULTS["relayout"])
     set_calibrate(*DEFAULTS["calibrate"])
+    set_run_share(*DEFAULTS["run_share"])
     set_tile_height(-1)
     set_tile_ctrl_out(1)
 
@@ -179,3 +189,38 @@ def jit_build_relayout(circuit: Circuit) -> int:
     n = ctypes.c_size_t(0)
     _lib.check(_lib.hip.qsim_jit_build_relayout(circuit.getNumQubits(), arr, cnt, ctypes.byref(n)))
     return n.value
+
+
+def plan_share_host(circuit: Circuit, calls: int, copies: int = 0, state=None):
+    """Play `calls` identical fused runs of the circuit through the engine's run-sharing
+    bookkeeping, every launched pass executed on the host with the staged kernels' index math,
+    flushed at the end (qsim_plan_share_host; no GPU).  Returns (state in logical order, circuit
+    passes launched per call, gates pending after each call)."""
+    n = circuit.getNumQubits()
+    arr, cnt = circuit.to_abi()
+    if state is None:
+        st = np.zeros(1 << n, np.complex128)
+        st[0] = 1.0
+    else:
+        st = np.array(state, dtype=np.complex128)
+    st = np.ascontiguousarray(st)
+    passes = np.zeros(max(1, calls), np.int32)
+    pending = np.zeros(max(1, calls), np.int32)
+    _lib.check(_lib.hip.qsim_plan_share_host(n, arr, cnt, copies, calls, st.ctypes.data_as(ctypes.c_void_p),
+                                             passes.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                             pending.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))))
+    return st, [int(x) for x in passes[:calls]], [int(x) for x in pending[:calls]]
+
+
+def plan_share_info(circuit: Circuit, copies: int = 0):
+    """(joint passes, single-run passes, highest copy per joint pass) of the joint plan a cycle of
+    `copies` runs would execute (qsim_plan_share_info, host only); joint passes = 0 and an empty
+    list when no cycle pays."""
+    n = circuit.getNumQubits()
+    arr, cnt = circuit.to_abi()
+    joint, single = ctypes.c_int(0), ctypes.c_int(0)
+    cap = 256
+    pc = (ctypes.c_int32 * cap)()
+    _lib.check(_lib.hip.qsim_plan_share_info(n, arr, cnt, copies, ctypes.byref(joint), ctypes.byref(single),
+                                             pc, cap))
+    return joint.value, single.value, [int(pc[k]) for k in range(min(cap, joint.value))]

@@ -196,6 +196,52 @@ int qsim_plan_exec_host(int n_qubits, const qsim_gate* gates, size_t count, int 
  * *passes = 0 when none exists. */
 int qsim_plan_relayout(int n_qubits, const qsim_gate* gates, size_t count, int32_t* perm, int* passes,
                        double* predicted_us);
+/* Run sharing (no reference counterpart).  A caller that runs the same circuit again and again
+ * before reading the state pays, per run, the edge effects a single plan cannot share.  When a
+ * fused qsim_run receives exactly the gate list of the previous fused qsim_run on the state (the
+ * lists are compared, not a hash), nothing is pending, the state's device pointer was not handed
+ * out and relayout plans are allowed for it, that call still runs its own plan whole and then
+ * arms a cycle: `copies` consecutive copies of the circuit are planned as ONE relayout plan (kept
+ * only if it needs fewer passes than `copies` single runs; memoised per circuit) and the state is
+ * brought to that plan's start layout by one gate-free pass.  Call j = 1..copies of the cycle then
+ * launches the longest prefix of the joint plan's not-yet-launched passes whose gates all belong
+ * to copies <= j; requested gates in later passes stay PENDING.  After call `copies` every pass
+ * has run, nothing is pending, and the next identical call starts the next cycle on the same
+ * plan with no planning and no upload.
+ * Contract: gates are applied no later than the next reader.  Every entry that reads or writes
+ * amplitudes (readout, sampling, measurement, expectation values, gradients, apply_gate / matrix
+ * entries, noise / density entries on the state, restore_layout, device_ptr, a qsim_run with
+ * another gate list or in per-gate mode) first flushes: the pending gates are lowered under the
+ * layout the state is in and run, in circuit order, as an ordinary fused plan, which ends the
+ * cycle.  qsim_state_init_zero / init_basis / from_host / destroy discard pending gates.
+ * qsim_state_sync waits for launched work and does not flush; qsim_state_last_run (the passes the
+ * last qsim_run call launched), layout_info, relayout, perm and the profile getters do not flush.
+ * Cost of arming: joint planning (once per circuit), under inline compilation the joint kernels'
+ * compile, and one extra pass over the state; a reader that ends a cycle early also pays the plan
+ * of the pending gates.  A reader between two identical runs prevents arming, and a state whose
+ * cycles are ended before one whole cycle has run backs off: after k such cycles in a row it lets
+ * 2^k - 1 (at most 63) identical repeats run unshared before it arms again.  A failure while
+ * arming (planning, compile, launch) leaves the run that triggered it successful and unshared.
+ * mode 0 off (every run executes its own plan, as before), 1 on (default, QSIM_RUN_SHARE) for
+ * states from the relayout size threshold; copies >= 2 (default 4, QSIM_RUN_SHARE_COPIES);
+ * negative arguments leave a setting unchanged.  QSIM_RUN_SHARE_TAIL (per cent, default 50, read
+ * once): the share of a copy's gates that must have run before a joint pass may also take gates
+ * of the next copy (100: from the start; fewer passes, but the first call of a cycle launches
+ * none). */
+int qsim_set_run_share(int mode, int copies);
+/* Host-only view of run sharing (tests; no GPU): plays `calls` identical fused runs of the
+ * circuit through the engine's cycle bookkeeping and executes every launched pass on the host
+ * with the staged kernels' index math (qsim_plan_exec_host), flushes at the end and returns the
+ * state in logical order.  amps: 2^n interleaved re/im, logical order, updated in place.
+ * passes_per_call / pending_per_call (calls entries each, may be null): the circuit passes each
+ * call launched and the gates pending after it.  copies <= 0: the configured count. */
+int qsim_plan_share_host(int n_qubits, const qsim_gate* gates, size_t count, int copies, int calls,
+                         double* amps, int32_t* passes_per_call, int32_t* pending_per_call);
+/* Host-only: the joint plan a cycle of `copies` runs would execute: its pass count (0: no cycle
+ * pays), the single-run plan's pass count, and per joint pass (up to cap entries, may be null) the
+ * highest copy (0-based) the pass holds a gate of. */
+int qsim_plan_share_info(int n_qubits, const qsim_gate* gates, size_t count, int copies, int* joint_passes,
+                         int* single_passes, int32_t* pass_copy, size_t cap);
 /* Layout calibration (with QSIM_JIT = 2, from min_qubits; defaults QSIM_RELABEL_CALIBRATE = 1,
  * QSIM_RELABEL_CALIBRATE_MIN_QUBITS = 26): the first run of a basis state times the layout
  * model's choice and two alternatives with their compiled pass kernels (the basis state is

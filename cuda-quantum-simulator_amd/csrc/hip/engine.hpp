@@ -566,6 +566,48 @@ void launch_expectation(const double2* st, int n, uint64_t batch, const ExpectPl
                         double* d_partials, double* d_out, hipStream_t s, Timer* tm);
 // The z lane/run split of groups of at least kExpectSplitMin terms (QSIM_EXPECT_SPLIT, default 1).
 constexpr int kExpectSplitMin = 16;
+bool expect_split_on();
+
+// Pauli-sum expectation values on a sharded state (dist_expect.hip; the transfers and collectives
+// around it: dist.hip).  A physical x mask splits into local bits (< L) and rank bits:
+// x = x_loc | x_rank << L.  Groups with x_rank == 0 pair inside a shard (launch_expectation on the
+// shard, n = L); a group with x_rank != 0 pairs shard r with shard r ^ x_rank and needs half of
+// the peer's shard.  Cross groups with the same key (x_rank, top local position in x_loc) share
+// one transfer; lower_expectation's order by x is already the order by key.
+struct DistExpectCross {
+    uint64_t x_rank, x_loc;
+    size_t begin, end;  // the group's terms in DistExpectPlan::all.terms
+    size_t xbegin;      // the same terms in the cross table (dist_expect_cross_terms)
+    size_t transfer;    // index of the transfer it reads
+};
+struct DistExpectTransfer {
+    uint64_t x_rank;
+    bool top;  // position L-1 is in x_loc
+};
+struct DistExpectPlan {
+    ExpectPlan all;                // lower_expectation over the n physical positions
+    std::vector<size_t> local;     // indices into all.groups with x_rank == 0
+    std::vector<DistExpectCross> cross;
+    std::vector<DistExpectTransfer> transfers;
+    size_t cross_terms = 0, launches = 0;  // launches: kernel launches per shard, both kinds
+};
+DistExpectPlan lower_dist_expectation(int n, int L, const qsim_pauli_term* terms, size_t count, const int* perm);
+// The tables of shard `rank`: z keeps its local bits, the sign (-1)^popcount(rank & z_rank) is
+// folded into cr / ci.  Local: a plan for launch_expectation with n = L.  Cross: the terms of
+// every cross group in plan order (group c at [xbegin, xbegin + end - begin)).
+ExpectPlan dist_expect_local(const DistExpectPlan& p, int L, int rank);
+std::vector<ExpectTerm> dist_expect_cross_terms(const DistExpectPlan& p, int L, int rank);
+// The half of its own shard (0 lower, 1 upper: the value of local bit L-1) that rank `rank`
+// pairs in a transfer's groups, and the half it sends to rank ^ x_rank.
+int dist_expect_own_half(const DistExpectTransfer& t, int rank);
+int dist_expect_send_half(const DistExpectTransfer& t, int rank);
+// *d_out (+)= sum over k < 2^(L-1) of W_re(i) Re a + W_im(i) Im a, i = k | half << (L-1) the local
+// index of own[k], a = conj(peer[k ^ (x_loc mod 2^(L-1))]) own[k]; W as in expect.hip over the
+// group's terms (d_terms: device, count terms, several launches past kExpectTerms).  own / peer:
+// 2^(L-1) amplitudes each; d_partials: expect_chunks(1) doubles.  Asynchronous.
+void launch_dist_expectation(const double2* own, const double2* peer, int L, int half, uint64_t x_loc,
+                             const ExpectTerm* d_terms, size_t count, double* d_partials, double* d_out,
+                             bool accumulate, hipStream_t s, Timer* tm);
 
 // Adjoint-method gradients (adjoint.hip).  A rotation's generator: pauli = 1 X, 2 Y, 3 Z on
 // position t (0: the identity, a plain inner product), times |1><1| on position c when c >= 0.

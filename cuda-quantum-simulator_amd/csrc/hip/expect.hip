@@ -209,14 +209,14 @@ __global__ __launch_bounds__(256) void k_expect_partial_split(const double2* st,
         partials[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
+}  // namespace
+
 // QSIM_EXPECT_SPLIT (default 1; read at every call, so a benchmark can time both kernels in one
 // process): 0 runs every group through the plain kernel.
 bool expect_split_on() {
     const char* e = std::getenv("QSIM_EXPECT_SPLIT");
     return e == nullptr || std::atoi(e) != 0;
 }
-
-}  // namespace
 
 void launch_expectation(const double2* st, int n, uint64_t batch, const ExpectPlan& plan, DevBuf& terms,
                         double* d_partials, double* d_out, hipStream_t s, Timer* tm) {

@@ -94,6 +94,17 @@ std::vector<double> DistributedSimulator::getProbabilities() const {
     return out;
 }
 
+double DistributedSimulator::expectation(const PauliSum& observable) const {
+    if (observable.getNumQubits() != num_qubits_)
+        throw std::invalid_argument("Observable qubit count doesn't match simulator");
+    std::vector<qsim_pauli_term> terms;
+    terms.reserve(observable.size());
+    for (const PauliSum::Term& t : observable.terms()) terms.push_back(qsim_pauli_term{t.x_mask, t.z_mask, t.coeff});
+    double e = 0.0;
+    check(qsim_dist_expectation(h_, terms.data(), terms.size(), &e));
+    return e;
+}
+
 void DistributedSimulator::setSeed(unsigned int seed) {
     rng_.seed(seed);
     seeded_ = true;

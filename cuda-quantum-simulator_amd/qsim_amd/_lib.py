@@ -243,6 +243,10 @@ _sig(hip, "qsim_dist_probabilities", [_P, _P])
 _sig(hip, "qsim_dist_sample", [_P, _P, c_int, _P])
 _sig(hip, "qsim_dist_collapse", [_P, c_int, c_int, c_double])
 _sig(hip, "qsim_dist_measure", [_P, c_int, c_double, POINTER(c_int)])
+_sig(hip, "qsim_dist_expectation", [_P, POINTER(qsim_pauli_term), c_size_t, POINTER(c_double)])
+_sig(hip, "qsim_dist_expectation_plan", [c_int, c_int, POINTER(c_int32), POINTER(qsim_pauli_term), c_size_t,
+                                         POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int),
+                                         POINTER(c_uint64)])
 _sig(hip, "qsim_dist_sample_plan", [c_int, c_int, POINTER(c_int32), POINTER(c_int), POINTER(c_uint64)])
 _sig(hip, "qsim_dist_profile", [_P, c_int])
 _sig(hip, "qsim_dist_profile_count", [_P, POINTER(c_int)])

@@ -187,6 +187,16 @@ class DistributedSimulator:
                                                     if root else None))
         return out
 
+    def expectation(self, observable) -> float:
+        """<psi|H|psi> of a PauliSum on the sharded state, the same float on every rank
+        (qsim_dist_expectation): each shard is read where it lies — no gather, no remap, perm()
+        unchanged; a string with X or Y on a qubit that sits on a rank position moves half a
+        shard between the two ranks it pairs."""
+        terms, count = observable.to_abi(self._n)
+        e = _c.c_double()
+        _lib.check(_lib.hip.qsim_dist_expectation(self._h, terms, count, _c.byref(e)))
+        return e.value
+
     def setSeed(self, seed: int) -> None:
         """Seed this rank's generator (StateVector.setSeed).  sample / measure* draw on rank 0 and
         broadcast, so the shots are rank 0's; with the same seed on every rank all generators
@@ -291,6 +301,29 @@ def sample_plan(n: int, world: int, perm: List[int]) -> Tuple[int, int]:
     c, m = _c.c_int(0), _c.c_uint64(0)
     _lib.check(_lib.hip.qsim_dist_sample_plan(n, world, p, _c.byref(c), _c.byref(m)))
     return c.value, m.value
+
+
+def expectation_plan(n: int, world: int, perm: Optional[List[int]], observable) -> dict:
+    """Host-only (qsim_dist_expectation_plan): what DistributedSimulator.expectation does for a
+    PauliSum (or a list of (x_mask, z_mask, coeff)) under qubit map `perm` (None: the identity):
+    {local_groups, cross_groups, transfers, launches, bytes_sent_per_rank}."""
+    if perm is not None and len(perm) != n:
+        raise ValueError("perm needs one entry per qubit")
+    if hasattr(observable, "to_abi"):
+        terms, count = observable.to_abi(n)
+    else:
+        items = list(observable)
+        count = len(items)
+        terms = (_lib.qsim_pauli_term * max(1, count))()
+        for i, (x, z, c) in enumerate(items):
+            terms[i].x_mask, terms[i].z_mask, terms[i].coeff = x, z, c
+    p = (_c.c_int32 * n)(*perm) if perm is not None else None
+    lg, cg, tr, la = _c.c_int(0), _c.c_int(0), _c.c_int(0), _c.c_int(0)
+    by = _c.c_uint64(0)
+    _lib.check(_lib.hip.qsim_dist_expectation_plan(n, world, p, terms, count, _c.byref(lg), _c.byref(cg),
+                                                   _c.byref(tr), _c.byref(la), _c.byref(by)))
+    return {"local_groups": lg.value, "cross_groups": cg.value, "transfers": tr.value,
+            "launches": la.value, "bytes_sent_per_rank": by.value}
 
 
 def plan_memo_clear() -> None:

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "Circuit.hpp"
+#include "Observable.hpp"
 #include "Simulator.hpp"
 
 struct qsim_dist;
@@ -47,6 +48,11 @@ public:
 
     std::vector<std::complex<double>> getStateVector() const;  // rank 0; empty elsewhere
     std::vector<double> getProbabilities() const;              // rank 0; empty elsewhere
+
+    // <psi|H|psi> of a Pauli sum (Observable.hpp) on the sharded state, the same value on every
+    // rank: every shard is read where it lies, nothing is gathered and no qubit moves
+    // (qsim_dist_expectation).  std::invalid_argument on a qubit-count mismatch.
+    double expectation(const PauliSum& observable) const;
 
     std::vector<int> sample(int n_shots);  // without collapse; the same shots on every rank
     int measureQubit(int qubit);           // reference semantics: index bit n-1-qubit (F2)

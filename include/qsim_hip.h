@@ -603,6 +603,24 @@ int qsim_dist_collapse(qsim_dist* d, int logical_bit, int result, double scale);
  * 0 : 1 with p0 = qsim_dist_prob_bit_zero, then collapse with scale 1 / sqrt(p(result)).  An
  * outcome of probability below 1e-15 fails with QSIM_ERR_RUNTIME. */
 int qsim_dist_measure(qsim_dist* d, int logical_bit, double u, int* result);
+/* qsim_state_expectation on the sharded state: <psi|H|psi>, the same double on every rank.  The
+ * state is read where it lies: the masks are mapped through the qubit map, no remap runs, and the
+ * map, the amplitudes and the buffers are left exactly as they are.  A group of terms whose
+ * physical x mask has no rank position is one read of each shard; one with rank positions x_rank
+ * pairs rank r with rank r ^ x_rank, and HALF of the peer's shard crosses the link (each pair is
+ * taken by one of the two ranks).  Groups with the same (x_rank, top local position in x) share a
+ * transfer, so a call makes at most 2 (world - 1) of them; the local groups and the kernels of
+ * one transfer run while the next transfer is in flight (QSIM_DIST_EXPECT_OVERLAP=0, read per
+ * call: one receive buffer, every transfer waited for).  Sums are added in a fixed order (groups
+ * in plan order, shards in rank order, one all-reduce of the ranks' totals per call): two calls on
+ * the same state and layout return bitwise-equal values.  Error codes: qsim_state_expectation's. */
+int qsim_dist_expectation(qsim_dist* d, const qsim_pauli_term* terms, size_t count, double* out);
+/* Host-only: what qsim_dist_expectation would do for qubit map `perm` (n entries; null: the
+ * identity) in a world of `world` ranks: the groups read inside a shard and across ranks, the
+ * half-shard transfers, the kernel launches per shard and the bytes one rank sends. */
+int qsim_dist_expectation_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* terms,
+                               size_t count, int* local_groups, int* cross_groups, int* transfers, int* launches,
+                               uint64_t* bytes_sent_per_rank);
 /* Host-only: what qsim_dist_sample would do for qubit map `perm` (n entries): the chunk size
  * (log2) and the set of logical qubits it must bring local first (0: no remap). */
 int qsim_dist_sample_plan(int n_qubits, int world, const int32_t* perm, int* chunk_log,

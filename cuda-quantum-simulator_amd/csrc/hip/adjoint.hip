@@ -239,17 +239,25 @@ void launch_pauli_apply(const double2* src, double2* dst, int n, const ExpectPla
     }
     terms.upload(plan.terms.data(), plan.terms.size() * sizeof(ExpectTerm), s);
     const ExpectTerm* d_terms = (const ExpectTerm*)terms.ptr;
-    const unsigned blocks = (unsigned)std::min<uint64_t>((N + 255) / 256, 1u << 16);
     bool first = true;
     for (const ExpectGroup& g : plan.groups) {
-        for (size_t t0 = g.begin; t0 < g.end; t0 += kExpectTerms) {
-            const int nterms = (int)std::min<size_t>(kExpectTerms, g.end - t0);
-            TimedLaunch tl(tm, "pauli_apply", (first ? 32.0 : 48.0) * (double)N, s);
-            hipLaunchKernelGGL(first ? k_pauli_apply<false> : k_pauli_apply<true>, dim3(blocks), dim3(256), 0, s, src,
-                               dst, N, g.x, d_terms + t0, nterms);
-            QSIM_HIPCHK(hipGetLastError());
-            first = false;
-        }
+        launch_pauli_apply_group(src, dst, n, g.x, d_terms + g.begin, g.end - g.begin, first, s, tm);
+        first = false;
+    }
+}
+
+void launch_pauli_apply_group(const double2* src, double2* dst, int n, uint64_t x, const ExpectTerm* d_terms,
+                              size_t count, bool first, hipStream_t s, Timer* tm) {
+    const uint64_t N = 1ull << n;
+    if (x >= N) fail(QSIM_ERR_INVALID_ARGUMENT, "x mask of a Pauli group outside the state");
+    const unsigned blocks = (unsigned)std::min<uint64_t>((N + 255) / 256, 1u << 16);
+    for (size_t t0 = 0; t0 < count; t0 += kExpectTerms) {
+        const int nterms = (int)std::min<size_t>(kExpectTerms, count - t0);
+        TimedLaunch tl(tm, "pauli_apply", (first ? 32.0 : 48.0) * (double)N, s);
+        hipLaunchKernelGGL(first ? k_pauli_apply<false> : k_pauli_apply<true>, dim3(blocks), dim3(256), 0, s, src, dst, N,
+                           x, d_terms + t0, nterms);
+        QSIM_HIPCHK(hipGetLastError());
+        first = false;
     }
 }
 

@@ -1245,6 +1245,7 @@ struct qsim_dist {
     ~qsim_dist() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
+        grad.reset();
         if (comm) {  // flush, bounded wait (non-blocking comm), then destroy; abort on trouble
             bool ok = ncclCommFinalize(comm) == ncclSuccess;
             if (!ok) {
@@ -1279,6 +1280,31 @@ struct qsim_dist {
     Scratch readout;  // sampling / probabilities / broadcast temporaries (dist readout entries)
     // per shard: the signed term tables of the last expectation value (dist_expect.hip)
     std::vector<std::unique_ptr<DevBuf>> expect_local, expect_cross;
+    // Adjoint-method gradients (gradient_dist): the two work shards per shard of this process, the
+    // per-shard term tables of H, the (parameter, shard) slots, and the plans of the inverted
+    // segments, keyed like run plans by (gate list, map at the start).  Absent until the first
+    // sweep; freed by qsim_dist_gradient_release and with the object.
+    struct GradSegment {
+        std::vector<qsim_gate> gates;
+        std::vector<int> perm_in, perm_out;
+        std::vector<std::vector<DStep>> steps;                        // per shard
+        std::vector<std::vector<std::unique_ptr<PlanCache>>> fplans;  // per shard, per step
+    };
+    struct GradWork {
+        std::vector<double2*> phi, lam;
+        std::vector<std::unique_ptr<DevBuf>> terms;
+        double* d_slots = nullptr;
+        size_t slots_cap = 0;
+        std::vector<std::unique_ptr<GradSegment>> segments;
+        ~GradWork() {
+            for (double2* p : phi)
+                if (p) (void)hipFree(p);
+            for (double2* p : lam)
+                if (p) (void)hipFree(p);
+            if (d_slots) (void)hipFree(d_slots);
+        }
+    };
+    std::unique_ptr<GradWork> grad;
 };
 
 namespace {
@@ -1586,11 +1612,14 @@ void own_slab_copy(qsim_dist* d, const Shard& sh, const XPlan& x, uint64_t base,
     QSIM_HIPCHK(hipMemcpyAsync(sh.recvbuf + at, sh.sendbuf + at, amps * sizeof(double2), hipMemcpyDeviceToDevice, s));
 }
 
-void exchange(qsim_dist* d, const DStep& ex, const std::vector<char>& fused) {
+// on: the shards to remap instead of the state's (the gradient's work states: their own
+// amplitudes, the state's staging buffers); null: the state.
+void exchange(qsim_dist* d, const DStep& ex, const std::vector<char>& fused, const std::vector<Shard>* on = nullptr) {
     if (ex.k == 0) return;
+    const std::vector<Shard>& shards = on ? *on : d->shards;
     const uint64_t total = 1ull << d->L;
     const uint64_t chunk = total >> ex.k;
-    const double bytes = 2.0 * 16.0 * (double)(total - chunk) * (double)d->shards.size();
+    const double bytes = 2.0 * 16.0 * (double)(total - chunk) * (double)shards.size();
     TimedLaunch tl(&d->timer, "alltoall_remap", bytes, d->stream);
     const int parts = pipeline_parts(chunk);
     int sub_log = d->L - ex.k;
@@ -1603,15 +1632,15 @@ void exchange(qsim_dist* d, const DStep& ex, const std::vector<char>& fused) {
             QSIM_HIPCHK(hipEventCreateWithFlags(&d->events[i], hipEventDisableTiming));
     }
     std::vector<XPlan> xs;
-    for (Shard& sh : d->shards) xs.push_back(xplan(d, sh, ex));
+    for (const Shard& sh : shards) xs.push_back(xplan(d, sh, ex));
     for (int p = 0; p < parts; ++p) {
-        for (size_t i = 0; i < d->shards.size(); ++i) {
+        for (size_t i = 0; i < shards.size(); ++i) {
             if (fused[i]) {  // (the pass before stored the slabs; the own slab moves on the device)
-                own_slab_copy(d, d->shards[i], xs[i], (uint64_t)p * sub, chunk, sub, d->stream);
+                own_slab_copy(d, shards[i], xs[i], (uint64_t)p * sub, chunk, sub, d->stream);
                 continue;
             }
             XArgs a = xs[i].a;
-            a.buf = d->shards[i].sendbuf;
+            a.buf = shards[i].sendbuf;
             copy_kernel(true, a, (uint64_t)p * sub, sub_log, d->stream);
         }
         QSIM_HIPCHK(hipEventRecord(d->events[p], d->stream));
@@ -1619,17 +1648,17 @@ void exchange(qsim_dist* d, const DStep& ex, const std::vector<char>& fused) {
     for (int p = 0; p < parts; ++p) {
         QSIM_HIPCHK(hipStreamWaitEvent(d->comm_stream, d->events[p], 0));
         std::vector<Post> posts;
-        for (size_t i = 0; i < d->shards.size(); ++i)
-            slab_posts(posts, d->shards[i], xs[i], ex.k, (uint64_t)p * sub, chunk, sub);
+        for (size_t i = 0; i < shards.size(); ++i)
+            slab_posts(posts, shards[i], xs[i], ex.k, (uint64_t)p * sub, chunk, sub);
         post_transfers(d, posts, "remap send/recv");
         QSIM_HIPCHK(hipEventRecord(d->events[parts + p], d->comm_stream));
     }
     for (int p = 0; p < parts; ++p) {
         QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[parts + p], 0));
-        for (size_t i = 0; i < d->shards.size(); ++i) {
+        for (size_t i = 0; i < shards.size(); ++i) {
             if (fused[i]) continue;  // (the step after loads the receive buffer itself)
             XArgs a = xs[i].a;
-            a.buf = d->shards[i].recvbuf;
+            a.buf = shards[i].recvbuf;
             copy_kernel(false, a, (uint64_t)p * sub, sub_log, d->stream);
         }
     }
@@ -2187,6 +2216,341 @@ double expectation_dist(qsim_dist* d, const qsim_pauli_term* terms, size_t count
     double local = 0.0;
     for (double v : slots) local += v;  // (slot order: local groups, then plan order; shards in rank order)
     return allreduce_sum(d, local);
+}
+
+// ---- adjoint-method gradients on the sharded state (kernels: dist_adjoint.hip) -------------
+void check_gradient_args(int n, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms, size_t nterms) {
+    if (!gates && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gate list");
+    if (!terms && nterms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
+    for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n);
+    const uint64_t valid = (1ull << n) - 1ull;  // (n <= QSIM_MAX_QUBITS_DIST < 64)
+    for (size_t t = 0; t < nterms; ++t)
+        if ((terms[t].x_mask | terms[t].z_mask) & ~valid)
+            fail(QSIM_ERR_OUT_OF_RANGE, "Pauli term acts on a qubit index out of range");
+}
+
+// The work shards (allocated on first use) and room for nparams x (shards + 1) slots.
+qsim_dist::GradWork& ensure_grad(qsim_dist* d, size_t nparams) {
+    if (!d->grad) d->grad = std::make_unique<qsim_dist::GradWork>();
+    qsim_dist::GradWork& w = *d->grad;
+    const size_t S = d->shards.size();
+    auto grab = [&](void** p, size_t b) {
+        if (*p) return;
+        if (hipMalloc(p, b) != hipSuccess) {
+            (void)hipGetLastError();  // (clear the sticky error: the state itself is intact)
+            *p = nullptr;
+            (void)hipStreamSynchronize(d->stream);
+            d->grad.reset();
+            fail(QSIM_ERR_DEVICE, "out of device memory for the gradient work shards");
+        }
+    };
+    w.phi.resize(S, nullptr);
+    w.lam.resize(S, nullptr);
+    for (size_t i = 0; i < S; ++i) {
+        grab((void**)&w.phi[i], sizeof(double2) << d->L);
+        grab((void**)&w.lam[i], sizeof(double2) << d->L);
+    }
+    const size_t need = nparams * (S + 1);
+    if (need > w.slots_cap) {
+        if (w.d_slots) {
+            QSIM_HIPCHK(hipStreamSynchronize(d->stream));
+            (void)hipFree(w.d_slots);
+            w.d_slots = nullptr;
+            w.slots_cap = 0;
+        }
+        const size_t cap = std::max<size_t>(need, 256);
+        grab((void**)&w.d_slots, cap * sizeof(double));
+        w.slots_cap = cap;
+    }
+    while (w.terms.size() < S) w.terms.emplace_back(new DevBuf());
+    return w;
+}
+
+// One inverted run of non-parameterised gates (execution order, logical qubits) on both work
+// states, from work map wperm (updated).  The sharded planner without its overlap marks: ops
+// steps as fused plans or per gate (flags), remaps whole, phi first, then lambda — the plan is a
+// function of (gates, start map), so both end under the same map.  Nothing of the state's own run
+// bookkeeping (map, counters, run plans, carry) is read or written.
+void grad_run_segment(qsim_dist* d, qsim_dist::GradWork& w, const std::vector<qsim_gate>& seg, std::vector<int>& wperm,
+                      int flags) {
+    if (seg.empty()) return;
+    const size_t S = d->shards.size();
+    qsim_dist::GradSegment* gs = nullptr;
+    for (auto& c : w.segments)
+        if (c->perm_in == wperm && c->gates.size() == seg.size() &&
+            std::memcmp(c->gates.data(), seg.data(), seg.size() * sizeof(qsim_gate)) == 0)
+            gs = c.get();
+    if (!gs) {
+        if (w.segments.size() >= 64) {  // (their compiled kernels may still be queued)
+            QSIM_HIPCHK(hipStreamSynchronize(d->stream));
+            w.segments.clear();
+        }
+        auto c = std::make_unique<qsim_dist::GradSegment>();
+        c->gates = seg;
+        c->perm_in = wperm;
+        for (const Shard& sh : d->shards) {
+            std::vector<int> perm = wperm;
+            c->steps.push_back(plan_dist_core(seg.data(), seg.size(), d->n, d->g, sh.rank, perm));
+            c->perm_out = perm;
+            c->fplans.emplace_back();
+            for (const DStep& st : c->steps.back())
+                c->fplans.back().push_back(st.kind == 0 ? std::make_unique<PlanCache>() : nullptr);
+        }
+        w.segments.push_back(std::move(c));
+        gs = w.segments.back().get();
+    }
+    for (size_t i = 1; i < S; ++i) {
+        if (gs->steps[i].size() != gs->steps[0].size()) fail(QSIM_ERR_RUNTIME, "exchange skeleton mismatch");
+        for (size_t k = 0; k < gs->steps[0].size(); ++k)
+            if (gs->steps[i][k].kind != gs->steps[0][k].kind) fail(QSIM_ERR_RUNTIME, "exchange skeleton mismatch");
+    }
+    const std::vector<char> unfused(S, 0);
+    for (const std::vector<double2*>* bufs : {&w.phi, &w.lam}) {
+        std::vector<Shard> ws = d->shards;  // (the state's staging buffers, the work state's amplitudes)
+        for (size_t i = 0; i < S; ++i) ws[i].d = (*bufs)[i];
+        for (size_t k = 0; k < gs->steps[0].size(); ++k) {
+            if (gs->steps[0][k].kind == 1) {
+                exchange(d, gs->steps[0][k], unfused, &ws);
+                continue;
+            }
+            for (size_t i = 0; i < S; ++i) {
+                const std::vector<Op>& ops = gs->steps[i][k].ops;
+                if (ops.empty()) continue;
+                const StepRun r = prepare_step(d, ops, flags, *gs->fplans[i][k], 0, 0);
+                run_part(d, ws[i], ops, r, 0, r.plan ? r.np : 1);
+            }
+        }
+    }
+    wperm = gs->perm_out;
+}
+
+// One parameterised step of the sweep: slots[i] = shard i's share of Im <lambda| G |phi>, then
+// U^† on both work states (last: the circuit's first rotation, after which nothing is read —
+// lambda is left as it is).  inv_gate: the inverse rotation on logical qubits.
+void grad_step(qsim_dist* d, qsim_dist::GradWork& w, const qsim_gate& inv_gate, const std::vector<int>& wperm,
+               double* slots, bool last, bool fused_step) {
+    const int L = d->L;
+    const size_t S = d->shards.size();
+    qsim_gate pg = inv_gate;  // physical positions over all n
+    for (int j = 0; j < pg.nqubits; ++j) pg.qubits[j] = wperm[inv_gate.qubits[j]];
+    const int cls = dist_gradient_class(inv_gate, wperm.data(), L);
+    const Generator gen = gate_generator(pg);
+    const bool crank = cls == DG_LOCAL_CRANK || cls == DG_DIAG_CRANK || cls == DG_CROSS_CRANK;
+    auto takes_part = [&](const Shard& sh) { return !crank || ((sh.rank >> (gen.c - L)) & 1); };
+    const int cpos = gen.c >= 0 && gen.c < L ? gen.c : -1;
+    if (cls == DG_LOCAL || cls == DG_LOCAL_CRANK) {
+        qsim_gate lg = pg;
+        Generator lgen = gen;
+        if (crank) {  // the control reads 1 on every amplitude of a shard that takes part
+            lg.type = pg.type == QSIM_GATE_CRY ? QSIM_GATE_RY : QSIM_GATE_RZ;
+            lg.nqubits = 1;
+            lg.qubits[0] = gen.t;
+            lgen.c = -1;
+        }
+        const Op inv = lower_gate(lg, L);
+        for (size_t i = 0; i < S; ++i) {
+            if (!takes_part(d->shards[i])) continue;
+            if (last || !fused_step)
+                launch_braket(w.lam[i], w.phi[i], L, lgen, d->d_partials, nullptr, slots + i, d->stream, &d->timer);
+            else
+                launch_adjoint_step(w.phi[i], w.lam[i], L, lgen, inv, d->d_partials, slots + i, d->stream, &d->timer);
+            if (!last && !fused_step) {
+                launch_op(w.phi[i], L, 1, inv, d->stream, &d->timer);
+                launch_op(w.lam[i], L, 1, inv, d->stream, &d->timer);
+            }
+        }
+        return;
+    }
+    const Op inv = lower_gate(pg, d->n);
+    const int tb = gen.t - L;  // the target's rank bit
+    if (cls == DG_DIAG || cls == DG_DIAG_CRANK) {
+        for (size_t i = 0; i < S; ++i)
+            if (takes_part(d->shards[i]))
+                launch_dist_adjoint_diag(w.phi[i], w.lam[i], L, cpos, (d->shards[i].rank >> tb) & 1, inv, d->d_partials,
+                                         slots + i, d->stream, &d->timer);
+        return;
+    }
+    // Rx / Ry / CRY across ranks.  Events 0 .. 2 of d->events (free outside remaps): the work
+    // states' last writers and the staging buffers' last readers are done (0), the peer's phi has
+    // landed in the receive buffer (1), its lambda in the send buffer (2).  Both transfers are
+    // queued before the first kernel, so lambda crosses while phi is updated; a shard is updated
+    // only after the transfer that sends it has completed.
+    if (d->world == 1) fail(QSIM_ERR_RUNTIME, "cross-rank gradient step in a world of one");
+    const uint64_t amps = 1ull << L;
+    QSIM_HIPCHK(hipEventRecord(d->events[0], d->stream));
+    QSIM_HIPCHK(hipStreamWaitEvent(d->comm_stream, d->events[0], 0));
+    for (int which = 0; which < (last ? 1 : 2); ++which) {
+        std::vector<Post> posts;
+        for (size_t i = 0; i < S; ++i) {
+            const Shard& sh = d->shards[i];
+            if (!takes_part(sh)) continue;
+            posts.push_back({sh.rank, sh.rank ^ (1 << tb), which ? w.lam[i] : w.phi[i], which ? sh.sendbuf : sh.recvbuf,
+                             amps});
+        }
+        post_transfers(d, posts, which ? "gradient lambda shard send/recv" : "gradient phi shard send/recv");
+        QSIM_HIPCHK(hipEventRecord(d->events[1 + which], d->comm_stream));
+    }
+    QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[1], 0));
+    for (size_t i = 0; i < S; ++i) {
+        const Shard& sh = d->shards[i];
+        if (takes_part(sh))
+            launch_dist_adjoint_step(w.phi[i], sh.recvbuf, w.lam[i], L, gen.pauli, cpos, (sh.rank >> tb) & 1, inv,
+                                     d->d_partials, slots + i, d->stream, &d->timer);
+    }
+    if (last) return;
+    QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[2], 0));
+    for (size_t i = 0; i < S; ++i) {
+        const Shard& sh = d->shards[i];
+        if (takes_part(sh))
+            launch_dist_adjoint_step(w.lam[i], sh.sendbuf, nullptr, L, gen.pauli, cpos, (sh.rank >> tb) & 1, inv,
+                                     d->d_partials, nullptr, d->stream, &d->timer);
+    }
+}
+
+// The value and the sweep of qsim_dist_gradient, on the state the forward run left.
+void gradient_dist(qsim_dist* d, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms, size_t nterms,
+                   int flags, double* value, double* grad) {
+    const int n = d->n, L = d->L;
+    const size_t S = d->shards.size();
+    *value = 0.0;
+    for (size_t k = 0; k < count; ++k) grad[k] = 0.0;
+    flush_carry(d);  // (the run's last step, if it was left pending)
+    const DistApplyPlan ap = lower_dist_apply(n, L, terms, nterms, d->perm.data());
+    if (ap.all.terms.empty()) {  // H = 0 (no terms, or every coefficient cancels): no sweep
+        stream_wait(d, d->stream);
+        return;
+    }
+    std::vector<size_t> params;
+    for (size_t k = 0; k < count; ++k)
+        if (gate_is_parameterised(gates[k].type)) params.push_back(k);
+    // (the work shards first: a failed allocation leaves nothing queued)
+    qsim_dist::GradWork* wp = params.empty() ? nullptr : &ensure_grad(d, params.size());
+    *value = expectation_dist(d, terms, nterms);
+    if (!wp) return;
+    qsim_dist::GradWork& w = *wp;
+    if (ap.cross_groups && d->world == 1) fail(QSIM_ERR_RUNTIME, "cross-rank Pauli group in a world of one");
+    if (d->events.size() < 5) {
+        const size_t have = d->events.size();
+        d->events.resize(5, nullptr);
+        for (size_t i = have; i < d->events.size(); ++i)
+            QSIM_HIPCHK(hipEventCreateWithFlags(&d->events[i], hipEventDisableTiming));
+    }
+    const double sent_before = d->sent_bytes;  // (remapBytes() stays the forward run's)
+    std::vector<int> wperm = d->perm;
+    const uint64_t amps = 1ull << L;
+    // phi: the state where it lies; lambda = H phi under the same map
+    for (size_t i = 0; i < S; ++i) {
+        QSIM_HIPCHK(hipMemcpyAsync(w.phi[i], d->shards[i].d, amps * sizeof(double2), hipMemcpyDeviceToDevice, d->stream));
+        const std::vector<ExpectTerm> tab = dist_apply_terms(ap, L, d->shards[i].rank);
+        w.terms[i]->upload(tab.data(), tab.size() * sizeof(ExpectTerm), d->stream);
+    }
+    std::vector<char> first(S, 1);
+    uint64_t landed = 0;  // x_rank of the phi shards in the receive buffers
+    for (const DistApplyGroup& g : ap.groups) {
+        if (g.x_rank != 0 && g.x_rank != landed) {
+            QSIM_HIPCHK(hipEventRecord(d->events[0], d->stream));  // phi written, the buffer's readers done
+            QSIM_HIPCHK(hipStreamWaitEvent(d->comm_stream, d->events[0], 0));
+            std::vector<Post> posts;
+            for (size_t i = 0; i < S; ++i) {
+                const Shard& sh = d->shards[i];
+                posts.push_back({sh.rank, (int)((uint64_t)sh.rank ^ g.x_rank), w.phi[i], sh.recvbuf, amps});
+            }
+            post_transfers(d, posts, "gradient H phi shard send/recv");
+            QSIM_HIPCHK(hipEventRecord(d->events[1], d->comm_stream));
+            QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[1], 0));
+            landed = g.x_rank;
+        }
+        for (size_t i = 0; i < S; ++i) {
+            const double2* src = g.x_rank ? d->shards[i].recvbuf : w.phi[i];
+            launch_pauli_apply_group(src, w.lam[i], L, g.x_loc, (const ExpectTerm*)w.terms[i]->ptr + g.begin,
+                                     g.end - g.begin, first[i] != 0, d->stream, &d->timer);
+            first[i] = 0;
+        }
+    }
+    // the sweep: slot [parameter j][shard i]
+    const size_t P = params.size();
+    QSIM_HIPCHK(hipMemsetAsync(w.d_slots, 0, P * (S + 1) * sizeof(double), d->stream));
+    const bool fused_step = adjoint_fused_on();
+    const size_t first_param = params.front();
+    std::vector<qsim_gate> seg;
+    size_t j = P;
+    for (size_t k = count; k-- > first_param;) {
+        const qsim_gate inv_gate = gate_inverse(gates[k]);
+        if (!gate_is_parameterised(gates[k].type)) {
+            seg.push_back(inv_gate);
+            continue;
+        }
+        grad_run_segment(d, w, seg, wperm, flags);
+        seg.clear();
+        --j;
+        grad_step(d, w, inv_gate, wperm, w.d_slots + j * S, k == first_param, fused_step);
+    }
+    // the shards of this process in rank order, then the ranks: one vector all-reduce
+    double* d_tot = w.d_slots + P * S;
+    launch_sum_partials(w.d_slots, (int)S, (unsigned)P, d_tot, false, d->stream);
+    std::vector<double> tot(P, 0.0);
+    allreduce_vec(d, d_tot, P, tot.data());
+    stream_wait(d, d->comm_stream);
+    for (size_t q = 0; q < P; ++q) grad[params[q]] = tot[q];
+    d->sent_bytes = sent_before;
+}
+
+// Host-only mirror of gradient_dist (qsim_dist_gradient_plan): the same classification and the
+// same planner calls, from map `perm`.
+void gradient_plan_host(int n, int g, std::vector<int> perm, const qsim_gate* gates, size_t count,
+                        const qsim_pauli_term* terms, size_t nterms, qsim_dist_gradient_info* out) {
+    const int L = n - g;
+    std::memset(out, 0, sizeof(*out));
+    if (count) (void)plan_dist_core(gates, count, n, g, 0, perm);  // the forward run's end map
+    for (int q = 0; q < n; ++q) out->perm_after_run[q] = out->perm_after_sweep[q] = perm[q];
+    std::vector<size_t> params;
+    for (size_t k = 0; k < count; ++k)
+        if (gate_is_parameterised(gates[k].type)) params.push_back(k);
+    out->params = (int32_t)params.size();
+    const DistApplyPlan ap = lower_dist_apply(n, L, terms, nterms, perm.data());
+    if (ap.all.terms.empty() || params.empty()) return;  // no sweep
+    out->apply_groups_local = (int32_t)ap.local_groups;
+    out->apply_groups_cross = (int32_t)ap.cross_groups;
+    out->apply_transfers = (int32_t)ap.transfers;
+    out->apply_launches = (int32_t)ap.launches;
+    std::vector<qsim_gate> seg;
+    const size_t first_param = params.front();
+    for (size_t k = count; k-- > first_param;) {
+        const qsim_gate inv_gate = gate_inverse(gates[k]);
+        if (!gate_is_parameterised(gates[k].type)) {
+            seg.push_back(inv_gate);
+            continue;
+        }
+        if (!seg.empty()) {
+            int remaps = 0;
+            for (const DStep& st : plan_dist_core(seg.data(), seg.size(), n, g, 0, perm)) remaps += st.kind == 1;
+            ++out->segments;
+            out->remap_segments += remaps > 0;
+            out->segment_remaps += remaps;
+            seg.clear();
+        }
+        const Generator gen = gate_generator(inv_gate);
+        const int cls = dist_gradient_class(inv_gate, perm.data(), L);
+        switch (cls) {
+            case DG_LOCAL:
+                ++out->steps_local;
+                if (gen.c >= 0) ++(perm[gen.c] < perm[gen.t] ? out->local_ctrl_below : out->local_ctrl_above);
+                break;
+            case DG_LOCAL_CRANK: ++out->steps_local_crank; break;
+            case DG_DIAG: ++out->steps_diag; break;
+            case DG_DIAG_CRANK: ++out->steps_diag_crank; break;
+            default:
+                ++(cls == DG_CROSS ? out->steps_cross : out->steps_cross_crank);
+                ++(inv_gate.type == QSIM_GATE_RX   ? out->cross_rx
+                   : inv_gate.type == QSIM_GATE_RY ? out->cross_ry
+                                                   : out->cross_cry);
+                out->step_transfers += k == first_param ? 1 : 2;  // (the first rotation needs phi alone)
+                break;
+        }
+    }
+    for (int q = 0; q < n; ++q) out->perm_after_sweep[q] = perm[q];
+    out->bytes_sent_per_rank =
+        (uint64_t)(out->apply_transfers + out->step_transfers) * ((uint64_t)sizeof(double2) << L);
 }
 }  // namespace
 
@@ -2880,6 +3244,65 @@ int qsim_dist_expectation_plan(int n_qubits, int world, const int32_t* perm, con
         *transfers = (int)plan.transfers.size();
         *launches = (int)plan.launches;
         *bytes_sent_per_rank = (uint64_t)plan.transfers.size() * (sizeof(double2) << (L - 1));
+    });
+}
+
+int qsim_dist_gradient(qsim_dist* d, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms,
+                       size_t nterms, int flags, double* value, double* grad) {
+    int rc = dguard([&] {
+        need(d);
+        if (!value) fail(QSIM_ERR_INVALID_ARGUMENT, "null value");
+        if (!grad && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gradient");
+        check_gradient_args(d->n, gates, count, terms, nterms);
+    });
+    if (rc != QSIM_OK) return rc;
+    // The forward run is qsim_dist_run itself: the state ends exactly as a plain run leaves it, and
+    // nothing below writes to it.
+    if (count > 0 && (rc = qsim_dist_run(d, gates, count, flags)) != QSIM_OK) return rc;
+    return dguard_comm(d, [&] {
+        QSIM_HIPCHK(hipSetDevice(d->device));
+        gradient_dist(d, gates, count, terms, nterms, flags, value, grad);
+    });
+}
+
+int qsim_dist_gradient_release(qsim_dist* d) {
+    return dguard([&] {
+        need(d);
+        if (!d->grad) return;
+        QSIM_HIPCHK(hipSetDevice(d->device));
+        QSIM_HIPCHK(hipStreamSynchronize(d->stream));
+        d->grad.reset();
+    });
+}
+
+int qsim_dist_gradient_memory_bytes(qsim_dist* d, uint64_t* bytes) {
+    return dguard([&] {
+        need(d);
+        if (!bytes) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
+        *bytes = 0;
+        if (!d->grad) return;
+        for (const auto* v : {&d->grad->phi, &d->grad->lam})
+            for (const double2* p : *v)
+                if (p) *bytes += sizeof(double2) << d->L;
+    });
+}
+
+int qsim_dist_gradient_plan(int n_qubits, int world, const int32_t* perm, const qsim_gate* gates, size_t count,
+                            const qsim_pauli_term* terms, size_t nterms, qsim_dist_gradient_info* out) {
+    return dguard([&] {
+        if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
+        const int g = log2_exact(world);
+        check_sizes(n_qubits, g);
+        check_gradient_args(n_qubits, gates, count, terms, nterms);
+        std::vector<int> p(n_qubits);
+        uint64_t seen = 0;
+        for (int q = 0; q < n_qubits; ++q) {
+            p[q] = perm ? perm[q] : q;
+            if (p[q] < 0 || p[q] >= n_qubits || ((seen >> p[q]) & 1ull))
+                fail(QSIM_ERR_INVALID_ARGUMENT, "qubit map is not a permutation");
+            seen |= 1ull << p[q];
+        }
+        gradient_plan_host(n_qubits, g, p, gates, count, terms, nterms, out);
     });
 }
 

@@ -57,7 +57,7 @@ DistExpectPlan lower_dist_expectation(int n, int L, const qsim_pauli_term* terms
     return p;
 }
 
-static ExpectTerm shard_term(const ExpectTerm& e, int L, int rank) {
+ExpectTerm dist_shard_term(const ExpectTerm& e, int L, int rank) {
     const uint64_t lmask = (1ull << L) - 1ull;
     const bool neg = __builtin_popcountll((uint64_t)rank & (e.z >> L)) & 1;
     return ExpectTerm{e.z & lmask, neg ? -e.cr : e.cr, neg ? -e.ci : e.ci};
@@ -68,7 +68,7 @@ ExpectPlan dist_expect_local(const DistExpectPlan& p, int L, int rank) {
     for (size_t gi : p.local) {
         const ExpectGroup& g = p.all.groups[gi];
         ExpectGroup lg{g.x, out.terms.size(), out.terms.size()};
-        for (size_t t = g.begin; t < g.end; ++t) out.terms.push_back(shard_term(p.all.terms[t], L, rank));
+        for (size_t t = g.begin; t < g.end; ++t) out.terms.push_back(dist_shard_term(p.all.terms[t], L, rank));
         lg.end = out.terms.size();
         out.groups.push_back(lg);
         out.launches += (lg.end - lg.begin + kExpectTerms - 1) / kExpectTerms;
@@ -80,7 +80,7 @@ std::vector<ExpectTerm> dist_expect_cross_terms(const DistExpectPlan& p, int L, 
     std::vector<ExpectTerm> out;
     out.reserve(p.cross_terms);
     for (const DistExpectCross& c : p.cross)
-        for (size_t t = c.begin; t < c.end; ++t) out.push_back(shard_term(p.all.terms[t], L, rank));
+        for (size_t t = c.begin; t < c.end; ++t) out.push_back(dist_shard_term(p.all.terms[t], L, rank));
     return out;
 }
 

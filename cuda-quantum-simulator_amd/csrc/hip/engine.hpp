@@ -633,6 +633,51 @@ void launch_braket(const double2* a, const double2* b, int n, const Generator& g
 void launch_adjoint_step(double2* phi, double2* lam, int n, const Generator& g, const Op& inv, double* d_partials,
                          double* d_out, hipStream_t s, Timer* tm);
 
+// One launch of it per kExpectTerms terms of one group: dst[i] (+)= W(i) src[i ^ x] over the
+// `count` device terms at d_terms; first: the first launch writes dst, later ones accumulate.
+void launch_pauli_apply_group(const double2* src, double2* dst, int n, uint64_t x, const ExpectTerm* d_terms,
+                              size_t count, bool first, hipStream_t s, Timer* tm);
+
+// Adjoint-method gradients on a sharded state (dist_adjoint.hip; the transfers, the inverted
+// segments and the collectives around it: dist.hip).
+// lambda = H phi on shards: lower_pauli_apply over the n physical positions, each group's x mask
+// split into x_loc | x_rank << L.  Groups come ordered by x, so groups of one x_rank are adjacent
+// and share the transfer of the peer's phi shard.
+struct DistApplyGroup {
+    uint64_t x_rank, x_loc;
+    size_t begin, end;  // the group's terms in DistApplyPlan::all.terms (and in a shard's table)
+};
+struct DistApplyPlan {
+    ExpectPlan all;
+    std::vector<DistApplyGroup> groups;  // plan order
+    size_t local_groups = 0, cross_groups = 0, transfers = 0, launches = 0;
+};
+DistApplyPlan lower_dist_apply(int n, int L, const qsim_pauli_term* terms, size_t count, const int* perm);
+// A term as shard `rank` sees it: the local z bits, the sign of the rank's z bits folded into cr / ci.
+ExpectTerm dist_shard_term(const ExpectTerm& e, int L, int rank);
+std::vector<ExpectTerm> dist_apply_terms(const DistApplyPlan& p, int L, int rank);  // all.terms for that shard
+// Class of a parameterised gate (logical qubits) under qubit map perm with L local positions.
+enum {
+    DG_LOCAL = 0,        // target local, control local or absent
+    DG_LOCAL_CRANK = 1,  // target local, control on a rank position
+    DG_DIAG = 2,         // Rz / CRZ, target on a rank position, control local or absent
+    DG_DIAG_CRANK = 3,   // ... control on a rank position
+    DG_CROSS = 4,        // Rx / Ry / CRY, target on a rank position, control local or absent
+    DG_CROSS_CRANK = 5   // ... control on a rank position
+};
+int dist_gradient_class(const qsim_gate& g, const int* perm, int L);
+// DG_DIAG step on one shard: *d_out = sgn Im <lam|phi> over the active indices (all 2^L, or those
+// with local bit cpos set when cpos >= 0), then both states times the entry of inv (K_DIAG, the
+// lowered inverse rotation) for this rank's target bit v.  d_partials: expect_chunks(1) doubles.
+void launch_dist_adjoint_diag(double2* phi, double2* lam, int L, int cpos, int v, const Op& inv, double* d_partials,
+                              double* d_out, hipStream_t s, Timer* tm);
+// DG_CROSS step, one work state on one shard: own <- row v of inv (K_M1) applied to (own, peer),
+// peer = the whole old shard of the rank whose target bit differs.  lam != null (own = phi):
+// first *d_out = this rank's share of Im <lam| G |phi>, G = X (pauli 1) or Y (2); lam == null: the
+// update alone (own = lambda, peer = the partner's old lambda).
+void launch_dist_adjoint_step(double2* own, const double2* peer, const double2* lam, int L, int pauli, int cpos, int v,
+                              const Op& inv, double* d_partials, double* d_out, hipStream_t s, Timer* tm);
+
 // ---------------------------------------------------------------------------------------
 // Timing (capi.hip): per-launch HIP events grouped by kernel name.
 // ---------------------------------------------------------------------------------------

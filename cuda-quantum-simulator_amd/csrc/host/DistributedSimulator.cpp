@@ -105,6 +105,26 @@ double DistributedSimulator::expectation(const PauliSum& observable) const {
     return e;
 }
 
+Gradient DistributedSimulator::gradient(const Circuit& circuit, const PauliSum& observable, RunMode mode) {
+    if (circuit.getNumQubits() != num_qubits_)
+        throw std::invalid_argument("Circuit qubit count doesn't match simulator");
+    if (observable.getNumQubits() != num_qubits_)
+        throw std::invalid_argument("Observable qubit count doesn't match simulator");
+    const std::vector<qsim_gate> gates = detail::toAbi(circuit);
+    std::vector<qsim_pauli_term> terms;
+    terms.reserve(observable.size());
+    for (const PauliSum::Term& t : observable.terms()) terms.push_back(qsim_pauli_term{t.x_mask, t.z_mask, t.coeff});
+    Gradient out{0.0, std::vector<double>(gates.size(), 0.0)};
+    check(qsim_dist_gradient(h_, gates.data(), gates.size(), terms.data(), terms.size(),
+                             mode == RunMode::Fused ? QSIM_RUN_FUSED : QSIM_RUN_PER_GATE, &out.value,
+                             out.gradient.data()));
+    return out;
+}
+
+void DistributedSimulator::releaseGradientBuffers() {
+    check(qsim_dist_gradient_release(h_));
+}
+
 void DistributedSimulator::setSeed(unsigned int seed) {
     rng_.seed(seed);
     seeded_ = true;

@@ -247,6 +247,21 @@ _sig(hip, "qsim_dist_expectation", [_P, POINTER(qsim_pauli_term), c_size_t, POIN
 _sig(hip, "qsim_dist_expectation_plan", [c_int, c_int, POINTER(c_int32), POINTER(qsim_pauli_term), c_size_t,
                                          POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                          POINTER(c_uint64)])
+class qsim_dist_gradient_info(Structure):
+    _fields_ = [(k, c_int32) for k in (
+        "params", "steps_local", "steps_local_crank", "steps_diag", "steps_diag_crank", "steps_cross",
+        "steps_cross_crank", "cross_rx", "cross_ry", "cross_cry", "local_ctrl_below", "local_ctrl_above",
+        "segments", "remap_segments", "segment_remaps", "apply_groups_local", "apply_groups_cross",
+        "apply_transfers", "apply_launches", "step_transfers")] + [
+        ("bytes_sent_per_rank", c_uint64), ("perm_after_run", c_int32 * 64), ("perm_after_sweep", c_int32 * 64)]
+
+
+_sig(hip, "qsim_dist_gradient", [_P, POINTER(qsim_gate), c_size_t, POINTER(qsim_pauli_term), c_size_t, c_int,
+                                 POINTER(c_double), POINTER(c_double)])
+_sig(hip, "qsim_dist_gradient_release", [_P])
+_sig(hip, "qsim_dist_gradient_memory_bytes", [_P, POINTER(c_uint64)])
+_sig(hip, "qsim_dist_gradient_plan", [c_int, c_int, POINTER(c_int32), POINTER(qsim_gate), c_size_t,
+                                      POINTER(qsim_pauli_term), c_size_t, POINTER(qsim_dist_gradient_info)])
 _sig(hip, "qsim_dist_sample_plan", [c_int, c_int, POINTER(c_int32), POINTER(c_int), POINTER(c_uint64)])
 _sig(hip, "qsim_dist_profile", [_P, c_int])
 _sig(hip, "qsim_dist_profile_count", [_P, POINTER(c_int)])

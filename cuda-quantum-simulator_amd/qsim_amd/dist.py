@@ -197,6 +197,35 @@ class DistributedSimulator:
         _lib.check(_lib.hip.qsim_dist_expectation(self._h, terms, count, _c.byref(e)))
         return e.value
 
+    def gradient(self, circuit: Circuit, observable, fused: bool = True):
+        """(value, gradient) on the sharded state (collective, qsim_dist_gradient): runs `circuit`
+        as run() would, then <psi|H|psi> and its derivative with respect to the angle of every
+        gate (numpy array, one entry per gate, 0 for a gate without a parameter) by one backward
+        sweep over two sharded work states.  A rotation whose target sits on a rank position
+        pairs each rank with one peer (two whole-shard transfers) instead of a remap.  The state,
+        perm() and the run counters are left as run() alone leaves them; every rank gets the
+        same floats."""
+        if circuit.getNumQubits() != self._n:
+            raise ValueError("Circuit qubit count doesn't match simulator")
+        arr, cnt = circuit.to_abi()
+        terms, nterms = observable.to_abi(self._n)
+        value = _c.c_double()
+        grad = np.zeros(max(1, cnt), dtype=np.float64)
+        _lib.check(_lib.hip.qsim_dist_gradient(
+            self._h, arr, cnt, terms, nterms, _lib.QSIM_RUN_FUSED if fused else _lib.QSIM_RUN_PER_GATE,
+            _c.byref(value), grad.ctypes.data_as(_c.POINTER(_c.c_double))))
+        return value.value, grad[:cnt]
+
+    def releaseGradientBuffers(self) -> None:
+        """Free the two work shards per rank gradient() keeps between calls."""
+        _lib.check(_lib.hip.qsim_dist_gradient_release(self._h))
+
+    def gradientMemoryBytes(self) -> int:
+        """Device bytes of the gradient work shards this process holds now."""
+        v = _c.c_uint64(0)
+        _lib.check(_lib.hip.qsim_dist_gradient_memory_bytes(self._h, _c.byref(v)))
+        return v.value
+
     def setSeed(self, seed: int) -> None:
         """Seed this rank's generator (StateVector.setSeed).  sample / measure* draw on rank 0 and
         broadcast, so the shots are rank 0's; with the same seed on every rank all generators
@@ -324,6 +353,34 @@ def expectation_plan(n: int, world: int, perm: Optional[List[int]], observable) 
                                                    _c.byref(tr), _c.byref(la), _c.byref(by)))
     return {"local_groups": lg.value, "cross_groups": cg.value, "transfers": tr.value,
             "launches": la.value, "bytes_sent_per_rank": by.value}
+
+
+def gradient_plan(circuit: Circuit, world: int, observable, perm: Optional[List[int]] = None) -> dict:
+    """Host-only (qsim_dist_gradient_plan): what DistributedSimulator.gradient does for `circuit`
+    and a PauliSum (or a list of (x_mask, z_mask, coeff)) when the call starts from a non-fresh
+    state with qubit map `perm` (None: the identity; a fresh state may relabel first, which is not
+    modelled): the parameterised steps by class, the inverted segments and their remaps, the
+    groups and transfers of lambda = H phi, the steps' transfers, bytes sent per rank, and the map
+    after the forward run and after the sweep."""
+    n = circuit.getNumQubits()
+    if perm is not None and len(perm) != n:
+        raise ValueError("perm needs one entry per qubit")
+    arr, cnt = circuit.to_abi()
+    if hasattr(observable, "to_abi"):
+        terms, count = observable.to_abi(n)
+    else:
+        items = list(observable)
+        count = len(items)
+        terms = (_lib.qsim_pauli_term * max(1, count))()
+        for i, (x, z, c) in enumerate(items):
+            terms[i].x_mask, terms[i].z_mask, terms[i].coeff = x, z, c
+    p = (_c.c_int32 * n)(*perm) if perm is not None else None
+    info = _lib.qsim_dist_gradient_info()
+    _lib.check(_lib.hip.qsim_dist_gradient_plan(n, world, p, arr, cnt, terms, count, _c.byref(info)))
+    out = {k: getattr(info, k) for k, _ in info._fields_ if not k.startswith("perm_")}
+    out["perm_after_run"] = list(info.perm_after_run[:n])
+    out["perm_after_sweep"] = list(info.perm_after_sweep[:n])
+    return out
 
 
 def plan_memo_clear() -> None:

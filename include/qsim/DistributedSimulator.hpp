@@ -54,6 +54,15 @@ public:
     // (qsim_dist_expectation).  std::invalid_argument on a qubit-count mismatch.
     double expectation(const PauliSum& observable) const;
 
+    // Simulator::gradient on the sharded state (collective, qsim_dist_gradient): runs `circuit` as
+    // run() would in `mode`, then <psi|H|psi> and its derivative with respect to the angle of every
+    // gate by one backward sweep over two sharded work states; a rotation whose target sits on a
+    // rank position pairs each rank with one peer instead of remapping.  The same values on every
+    // rank; the state and its qubit map are left as run() leaves them.  std::invalid_argument on a
+    // qubit-count mismatch.
+    Gradient gradient(const Circuit& circuit, const PauliSum& observable, RunMode mode = RunMode::Fused);
+    void releaseGradientBuffers();  // free the two work shards per rank gradient() keeps between calls
+
     std::vector<int> sample(int n_shots);  // without collapse; the same shots on every rank
     int measureQubit(int qubit);           // reference semantics: index bit n-1-qubit (F2)
 

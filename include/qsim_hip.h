@@ -621,6 +621,72 @@ int qsim_dist_expectation(qsim_dist* d, const qsim_pauli_term* terms, size_t cou
 int qsim_dist_expectation_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* terms,
                                size_t count, int* local_groups, int* cross_groups, int* transfers, int* launches,
                                uint64_t* bytes_sent_per_rank);
+/* qsim_state_gradient on the sharded state (collective).  Runs the circuit exactly as
+ * qsim_dist_run(d, gates, count, flags) would (fresh-state relabel, plan cache; a carried step is
+ * flushed first, as by every reader), then *value = <psi|H|psi> as qsim_dist_expectation computes
+ * it and grad[k] = dE/d(parameter of gate k) for Rx / Ry / Rz / CRY / CRZ, 0.0 for any other gate,
+ * by one backward sweep over two sharded work states phi and lambda = H phi.  Afterwards the
+ * state, qsim_dist_perm and what the run getters report are what qsim_dist_run alone leaves, the
+ * amplitudes bit for bit: the sweep never writes to the state's shards.
+ * The work states are read under a qubit map of their own that starts as the state's.  H phi: a
+ * group of terms whose physical x mask has no rank position is one pass over each shard; groups
+ * with rank positions x_rank read the WHOLE phi shard of rank r ^ x_rank, one transfer per distinct
+ * x_rank.  A parameterised step, by the physical positions of its target t and control c:
+ *   t local, c local or absent: the single-GPU step on each shard (QSIM_ADJOINT_FUSED=0 composes
+ *     it from a reduction and two per-gate launches, as there; the variable has no effect on the
+ *     classes below, which always use their own kernels);
+ *   t local, c on a rank position: the uncontrolled step on the ranks whose bit is 1;
+ *   Rz / CRZ with t on a rank position: one streaming kernel per shard, no transfer;
+ *   Rx / Ry / CRY with t on a rank position: rank r pairs with the rank whose t bit differs and
+ *     receives its whole old phi shard, then its whole old lambda shard (two transfers, the second
+ *     in flight while the first kernel runs; with a local control the whole shard still crosses,
+ *     the kernel touches the c == 1 half); the circuit's first rotation needs phi alone.
+ *   With c on a rank position only the ranks whose bit is 1 take part.
+ * Runs of other gates between rotations are inverted and run on both work states through the
+ * sharded planner (remaps included) from the work map, which they may change; they never touch the
+ * state's map, counters or cached run plans.  The sweep stops at the circuit's first rotation.
+ * Every (parameter, shard) sum has a slot of its own, the shards of a process are added in rank
+ * order and ONE vector all-reduce adds the ranks: every rank returns the same doubles and two
+ * calls return bitwise-equal results.  Work memory: two extra shards per rank, allocated by the
+ * first call that sweeps, kept until qsim_dist_gradient_release or qsim_dist_destroy; the
+ * exchange staging buffers serve the transfers (a world of one has and needs none).
+ * count == 0: the value of the state as it is (no run); nterms == 0 (or H == 0): value 0, zero
+ * gradient, no sweep, no allocation.  Null pointers -> QSIM_ERR_INVALID_ARGUMENT, a mask bit >= n
+ * -> QSIM_ERR_OUT_OF_RANGE, a bad gate -> the code of qsim_dist_run, work shards that cannot be
+ * allocated -> QSIM_ERR_DEVICE with the state holding U|psi0>.  Synchronises. */
+int qsim_dist_gradient(qsim_dist* d, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms,
+                       size_t nterms, int flags, double* value, double* grad);
+int qsim_dist_gradient_release(qsim_dist* d); /* free the work shards now */
+/* Device bytes of the gradient work shards this process holds now (0 before the first sweep and
+ * after a release). */
+int qsim_dist_gradient_memory_bytes(qsim_dist* d, uint64_t* bytes);
+/* Host-only: what qsim_dist_gradient would do, the qubit map simulated through the forward plan
+ * and the sweep.  Valid when the call starts from a non-fresh state with map `perm` (null: the
+ * identity): a fresh state (create / reset) may relabel its local positions first, which this
+ * entry does not model.  A step transfer or an apply transfer moves one whole shard
+ * (16 << (n - log2 world) bytes); bytes_sent_per_rank = (apply_transfers + step_transfers) x that:
+ * what a rank whose control bits are all 1 sends outside the segments' remaps. */
+typedef struct qsim_dist_gradient_info {
+    int32_t params;             /* parameterised gates */
+    int32_t steps_local;        /* t local, c local or absent */
+    int32_t steps_local_crank;  /* t local, c on a rank position */
+    int32_t steps_diag;         /* Rz / CRZ, t on a rank position, c local or absent */
+    int32_t steps_diag_crank;   /* ... c on a rank position */
+    int32_t steps_cross;        /* Rx / Ry / CRY, t on a rank position, c local or absent */
+    int32_t steps_cross_crank;  /* ... c on a rank position */
+    int32_t cross_rx, cross_ry, cross_cry;     /* the cross steps (both kinds) by gate type */
+    int32_t local_ctrl_below, local_ctrl_above; /* steps_local with a control below / above the target */
+    int32_t segments;           /* inverted runs of non-parameterised gates */
+    int32_t remap_segments;     /* ... that need at least one remap */
+    int32_t segment_remaps;     /* remaps of all segments, per work state */
+    int32_t apply_groups_local, apply_groups_cross, apply_transfers, apply_launches; /* lambda = H phi */
+    int32_t step_transfers;     /* whole-shard transfers of the cross steps */
+    uint64_t bytes_sent_per_rank;
+    int32_t perm_after_run[64]; /* the state's map after the forward run (the sweep's first map) */
+    int32_t perm_after_sweep[64]; /* the work map when the sweep ends */
+} qsim_dist_gradient_info;
+int qsim_dist_gradient_plan(int n_qubits, int world, const int32_t* perm, const qsim_gate* gates, size_t count,
+                            const qsim_pauli_term* terms, size_t nterms, qsim_dist_gradient_info* out);
 /* Host-only: what qsim_dist_sample would do for qubit map `perm` (n entries): the chunk size
  * (log2) and the set of logical qubits it must bring local first (0: no remap). */
 int qsim_dist_sample_plan(int n_qubits, int world, const int32_t* perm, int* chunk_log,

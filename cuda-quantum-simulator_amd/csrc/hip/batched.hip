@@ -200,9 +200,11 @@ __device__ __forceinline__ double2 mul_ipow(double2 a, int e) {
 
 // new[j] = i^e (-1)^{popc(z & (j^x))} old[j^x]; pairs (j, j^x) with bit h of j == 0.
 __global__ __launch_bounds__(256) void k_pauli_apply(double2* st, int n, const uint64_t* xz,
-                                                     const int* ephase, uint64_t items_per_traj) {
+                                                     const int* ephase, uint64_t items_per_traj,
+                                                     uint64_t batch) {
     const uint64_t item = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const uint64_t b = item / items_per_traj;
+    if (b >= batch) return;  // (the last block's surplus threads)
     const uint64_t k = item - b * items_per_traj;
     const uint64_t x = xz[2 * b], z = xz[2 * b + 1];
     const int e = ephase[b];
@@ -510,7 +512,7 @@ void materialize(qsim_batch* b) {
     const uint64_t total = items_per_traj * (uint64_t)b->batch;
     TimedLaunch tl(&b->timer, "pauli_apply", 0.0, b->stream);
     hipLaunchKernelGGL(k_pauli_apply, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, b->stream, b->d, b->n,
-                       b->d_xz, b->d_e, items_per_traj);
+                       b->d_xz, b->d_e, items_per_traj, (uint64_t)b->batch);
     QSIM_HIPCHK(hipGetLastError());
 }
 // Undo the relabeling in every trajectory (fused SWAP network over the batch, exact data
@@ -864,7 +866,8 @@ int qsim_batch_run(qsim_batch* b, const qsim_gate* gates, size_t count,
                 const uint64_t total = items_per_traj * (uint64_t)b->batch;
                 TimedLaunch tl(&b->timer, "pauli_apply", 0.0, b->stream);
                 hipLaunchKernelGGL(k_pauli_apply, dim3((unsigned)((total + 255) / 256)), dim3(256),
-                                   0, b->stream, b->d, b->n, b->d_xz, b->d_e, items_per_traj);
+                                   0, b->stream, b->d, b->n, b->d_xz, b->d_e, items_per_traj,
+                                   (uint64_t)b->batch);
                 QSIM_HIPCHK(hipGetLastError());
             }
         }

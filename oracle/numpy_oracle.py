@@ -13,6 +13,13 @@ Two implementations, written differently on purpose:
     loaded from oracle/build/libqsim_oracle.so.
 The two are cross-checked in tests/test_oracle.py and both against the reference's known-answer
 vectors in tests/golden/.
+
+Noise processes restated on top of them (each section below says what it restates):
+  * NoisySimulator: `noise_pass`, `noisy_run`
+  * BatchedSimulator, reference noise process: `batched_reference_run`
+  * BatchedSimulator, physical noise process (one Pauli draw per trajectory, channel and gate,
+    csrc/hip/batched.hip): `batched_physical_draws`, `batched_physical_run`
+  * DensityMatrixSimulator: `dm_run`
 """
 from __future__ import annotations
 
@@ -343,10 +350,6 @@ def noisy_run(n, gates, channels, seed, counter=0, state=None):
     return s, counter
 
 
-# ---- DensityMatrixSimulator (test infrastructure) ----------------------------------------
-# rho' = U rho U^dag with textbook matrices, channels per the reference kernels
-# src/DensityMatrix.cu:978-1122 (depolarizing: off-diagonal x (1 - 4p/3) only; bit-phase flip =
-# phase flip, :343-356; amplitude damping with the pre-channel rho11).
 # ---- BatchedSimulator, reference noise process (test infrastructure) ---------------------
 # Restates run() + applyBatchedNoise() + applyBatchedDepolarizingKernel
 # (src/NoiseModel.cu:815-892): after EVERY circuit gate (also gates the reference gate set
@@ -401,6 +404,77 @@ def batched_reference_run(n, B, gates, channels, seed, reference_gateset=False, 
     return st, counter
 
 
+# ---- BatchedSimulator, physical noise process (test infrastructure) ----------------------
+# Restates the draw law documented in csrc/hip/batched.hip (draw_step): after every circuit gate,
+# every Pauli-type channel entry draws once per trajectory from a stateless counter hash keyed by
+# (seed, step, channel, global trajectory index).  The picks are applied here one after another as
+# textbook X / Y / Z matrices on the trajectory's state: no composed Pauli string, no frames, no
+# Clifford propagation — those are the engine's (batched.hip, fused.hip) and are what this checks.
+_PHYS_PAULI_OF = {3: 0, 5: 1, 4: 2}  # BitFlip -> X, BitPhaseFlip -> Y, PhaseFlip -> Z (gate types)
+_TWO_M53 = 2.0 ** -53
+
+
+def _physical_channels(channels):
+    """The entries the physical process draws for, in model order: Depolarizing (0), BitFlip (3),
+    PhaseFlip (4), BitPhaseFlip (5); damping entries (1, 2) are dropped."""
+    return [(int(t), int(q), float(p)) for (t, q, p) in channels if int(t) in (0, 3, 4, 5)]
+
+
+def batched_physical_draws(channels, seed, step, traj):
+    """The Pauli picks of one step of one trajectory: a list of (pauli, qubit) in channel order,
+    pauli 0 X / 1 Y / 2 Z (== the gate type of that Pauli).
+
+    channels: (type, qubit, p) entries of the model in order.  Damping entries are dropped BEFORE
+    indexing: the channel index c that enters the hash key is the index in the filtered list, so
+    a model with damping entries interleaved draws exactly what the model without them draws (the
+    engine's behaviour, pinned by tests/test_batched_physical_cpu.py).  traj is the global
+    trajectory index (trajectory offset + index in the object).  All arithmetic is mod 2^64:
+      key = mix(seed ^ mix(step * 0x100000001b3 + c) ^ (traj << 20))
+      r1  = (mix(key) >> 11) * 2^-53;  the entry fires when r1 < p
+      Depolarizing: r2 = (mix(key ^ 0x5bd1e995) >> 11) * 2^-53; X below 1/3, Y below 2/3, else Z."""
+    picks = []
+    for c, (t, q, p) in enumerate(_physical_channels(channels)):
+        key = _mix((seed & _M64) ^ _mix((step * 0x100000001b3 + c) & _M64) ^ ((traj << 20) & _M64))
+        r1 = (_mix(key) >> 11) * _TWO_M53
+        if not r1 < p:
+            continue
+        if t == 0:
+            r2 = (_mix(key ^ 0x5bd1e995) >> 11) * _TWO_M53
+            pauli = 0 if r2 < 1.0 / 3.0 else (1 if r2 < 2.0 / 3.0 else 2)
+        else:
+            pauli = _PHYS_PAULI_OF[t]
+        picks.append((pauli, q))
+    return picks
+
+
+def batched_physical_run(n, B, gates, channels, seed, step=0, traj0=0, reference_gateset=False,
+                         states=None):
+    """channels: (type, qubit, p) entries in order; returns (states (B, 2^n), next step).
+    Every circuit gate (run_cpu; skipped when the reference gate set ignores it), then that
+    step's picks of every trajectory as X / Y / Z matrices in channel order.  The step counter
+    advances by one per circuit gate, skipped gates included, and only when the model has at least
+    one Pauli-type entry (as the engine's)."""
+    st = np.zeros((B, 1 << n), complex) if states is None else np.array(states, dtype=complex)
+    if states is None:
+        st[:, 0] = 1.0
+    drawing = bool(_physical_channels(channels))
+    for g in gates:
+        acts = not reference_gateset or g[0] in _REF_BATCH_GATES
+        for b in range(B):
+            s = run_cpu(n, [g], st[b]) if acts else st[b]
+            if drawing:
+                for pauli, q in batched_physical_draws(channels, seed, step, traj0 + b):
+                    s = apply_numpy(s, n, (pauli, [q], 0.0))
+            st[b] = s
+        if drawing:
+            step += 1
+    return st, step
+
+
+# ---- DensityMatrixSimulator (test infrastructure) ----------------------------------------
+# rho' = U rho U^dag with textbook matrices, channels per the reference kernels
+# src/DensityMatrix.cu:978-1122 (depolarizing: off-diagonal x (1 - 4p/3) only; bit-phase flip =
+# phase flip, :343-356; amplitude damping with the pre-channel rho11).
 def dm_apply_gate(rho, n, gate):
     t, qubits, th = gate
     if t in (13, 14, 16):

@@ -1,7 +1,11 @@
 """Batched trajectories on fused tile passes (batched.hip + fused.hip): the Pauli-frame execution
 must give exactly the trajectories of the per-gate execution (one kernel per gate and one Pauli
 pass per noisy step — the reference's structure, src/NoiseModel.cu:815-892) for the same seed,
-and noise-free trajectories must equal the oracle state."""
+and noise-free trajectories must equal the oracle state.
+
+Both executions share the draw law and the final Pauli pass, so these tests compare the engine
+with itself; parity of the noisy trajectories with an oracle written outside the engine
+(oracle/numpy_oracle.py: batched_physical_run) is tests/test_batched_physical_gpu.py's."""
 import numpy as np
 import pytest
 

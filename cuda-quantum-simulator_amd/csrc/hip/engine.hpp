@@ -568,6 +568,38 @@ void launch_expectation(const double2* st, int n, uint64_t batch, const ExpectPl
 constexpr int kExpectSplitMin = 16;
 bool expect_split_on();
 
+// Pauli-sum expectation values Re Tr(rho H) of a density matrix (dm_expect.hip).  Terms are merged
+// and grouped by logical x mask (one generalised diagonal of rho, 2^n elements, per group) and a
+// group is cut into rows of at most kExpectTerms terms with complex weights c i^nY (cr + i ci, z:
+// the LOGICAL z mask); one launch runs a (chunks of i, rows) grid, at most kDmExpectMaxRows rows.
+constexpr size_t kDmExpectMaxRows = 65535;  // the grid's y limit
+constexpr unsigned kDmExpectChunks = 128;   // work-groups along i (256 values of i per run)
+struct DmExpectMap {
+    uint64_t both[QSIM_DM_MAX_QUBITS];  // physical row bit | column bit of qubit q
+};
+struct DmExpectRow {
+    uint64_t xcol;          // the group's x mask at the physical column positions
+    uint32_t begin, count;  // the row's terms in DmExpectPlan::terms
+};
+struct DmExpectPlan {
+    int n = 0;
+    DmExpectMap map{};
+    std::vector<ExpectTerm> terms;
+    std::vector<DmExpectRow> rows;
+    size_t groups = 0, launches = 0;
+};
+// perm: the 2n index bits' logical -> physical map (null: identity).  Throws Error: n outside
+// [1, QSIM_DM_MAX_QUBITS] or a perm that is no permutation (invalid argument), a mask bit >= n (out
+// of range).
+DmExpectPlan lower_dm_expectation(int n, const qsim_pauli_term* terms, size_t count, const int* perm);
+unsigned dm_expect_chunks(int n);
+size_t dm_expect_work_doubles(const DmExpectPlan& plan);  // doubles of d_work a plan's launches need
+// *d_out = the plan's sum over rho (a 2n-bit state's current buffer); table: the owner's device copy
+// of the rows and terms (uploaded here).  Partial sums are added in a fixed order (no atomics).
+// Nothing is launched for a plan without rows.  Asynchronous.
+void launch_dm_expectation(const double2* rho, const DmExpectPlan& plan, DevBuf& table, double* d_work,
+                           double* d_out, hipStream_t s, Timer* tm);
+
 // Pauli-sum expectation values on a sharded state (dist_expect.hip; the transfers and collectives
 // around it: dist.hip).  A physical x mask splits into local bits (< L) and rank bits:
 // x = x_loc | x_rank << L.  Groups with x_rank == 0 pair inside a shard (launch_expectation on the

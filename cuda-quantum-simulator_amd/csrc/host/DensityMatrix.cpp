@@ -7,6 +7,7 @@
 #include <string>
 
 #include "abi_util.hpp"
+#include "qsim/Observable.hpp"
 
 namespace qsim {
 
@@ -43,6 +44,17 @@ std::vector<double> DensityMatrix::getProbabilities() const {
 double DensityMatrix::trace() const {
     const std::vector<double> p = getProbabilities();
     return std::accumulate(p.begin(), p.end(), 0.0);
+}
+
+double DensityMatrix::expectation(const PauliSum& observable) const {
+    if (observable.getNumQubits() != n_qubits_)
+        throw std::invalid_argument("Observable qubit count doesn't match simulator");
+    std::vector<qsim_pauli_term> terms;
+    terms.reserve(observable.size());
+    for (const PauliSum::Term& t : observable.terms()) terms.push_back(qsim_pauli_term{t.x_mask, t.z_mask, t.coeff});
+    double e = 0.0;
+    check(qsim_dm_expectation(rho_.handle(), n_qubits_, terms.data(), terms.size(), &e));
+    return e;
 }
 
 bool DensityMatrix::isValid(double tolerance) const {

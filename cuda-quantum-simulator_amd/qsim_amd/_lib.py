@@ -194,6 +194,9 @@ _sig(hip, "qsim_dm_apply_channel", [_P, c_int, c_int, c_int, c_double])
 _sig(hip, "qsim_dm_diagonal", [_P, c_int, _P])
 _sig(hip, "qsim_dm_init_pure", [_P, c_int, _P])
 _sig(hip, "qsim_dm_init_maximally_mixed", [_P, c_int])
+_sig(hip, "qsim_dm_expectation", [_P, c_int, POINTER(qsim_pauli_term), c_size_t, POINTER(c_double)])
+_sig(hip, "qsim_dm_expectation_plan", [c_int, POINTER(qsim_pauli_term), c_size_t, POINTER(c_int32), POINTER(c_int),
+                                       POINTER(c_int), POINTER(c_int), POINTER(c_uint64)])
 
 # ---- multi-GPU (sharded) state
 class qsim_op(Structure):

@@ -64,6 +64,14 @@ class DensityMatrix:
     def getMatrix(self) -> np.ndarray:
         return self._sv.toHost().reshape(1 << self._n, 1 << self._n)
 
+    def expectation(self, observable) -> float:
+        """Re Tr(rho H) of a PauliSum over the n qubits, reduced on the device where rho lies: no
+        readback and no layout restore (qsim_dm_expectation; no reference counterpart)."""
+        terms, count = observable.to_abi(self._n)
+        e = _c.c_double()
+        _lib.check(_lib.hip.qsim_dm_expectation(self._sv.handle, self._n, terms, count, _c.byref(e)))
+        return e.value
+
     def trace(self) -> float: return float(np.sum(self.getProbabilities()))
     def purity(self) -> float: return self._sv.getTotalProbability()  # sum |rho_ij|^2 (:147-167)
 
@@ -128,6 +136,7 @@ class DensityMatrixSimulator:
 
     def getProbabilities(self) -> np.ndarray: return self._rho.getProbabilities()
     def getDensityMatrix(self) -> np.ndarray: return self._rho.getMatrix()
+    def expectation(self, observable) -> float: return self._rho.expectation(observable)
     def getPurity(self) -> float: return self._rho.purity()
     def getTrace(self) -> float: return self._rho.trace()
     def getNumQubits(self) -> int: return self._rho.getNumQubits()

@@ -1,7 +1,8 @@
 """Pauli-sum observables H = sum_t c_t P_t (mirror of include/qsim/Observable.hpp).
 
 No reference counterpart: the reference has no observable API.  The expectation values are
-computed by the HIP engine where the state lies (qsim_state_expectation / qsim_batch_expectation).
+computed by the HIP engine where the state lies (qsim_state_expectation / qsim_batch_expectation;
+Re Tr(rho H) on a density matrix: qsim_dm_expectation).
 """
 from __future__ import annotations
 

@@ -37,6 +37,10 @@ public:
     double trace() const;
     double purity() const { return rho_.getTotalProbability(); }  // sum |rho_ij|^2
     bool isValid(double tolerance = 1e-10) const;
+    // Re Tr(rho H) of a Pauli sum over the n qubits (Observable.hpp), reduced on the device where
+    // rho lies: no readback and no layout restore (qsim_dm_expectation).  std::invalid_argument
+    // when the observable's qubit count differs.  No reference counterpart.
+    double expectation(const PauliSum& observable) const;
 
     Amplitude* getDevicePtr() { return rho_.devicePtr(); }
     StateVector& state() { return rho_; }
@@ -57,6 +61,7 @@ public:
 
     std::vector<double> getProbabilities() const { return rho_.getProbabilities(); }
     std::vector<std::complex<double>> getDensityMatrix() const { return rho_.getMatrix(); }
+    double expectation(const PauliSum& observable) const { return rho_.expectation(observable); }
     double getPurity() const { return rho_.purity(); }
     double getTrace() const { return rho_.trace(); }
     int measureQubit(int qubit);  // index bit `qubit` (src/DensityMatrix.cu:374-406)

@@ -4,7 +4,9 @@
 // Their expectation values are computed on the device where the state lies
 // (qsim_state_expectation / qsim_batch_expectation, include/qsim_hip.h): StateVector::expectation,
 // Simulator::expectation, NoisySimulator::expectation, BatchedSimulator::getExpectations; on a
-// sharded state DistributedSimulator::expectation (qsim_dist_expectation).
+// sharded state DistributedSimulator::expectation (qsim_dist_expectation); on a density matrix
+// DensityMatrix::expectation and DensityMatrixSimulator::expectation, Re Tr(rho H)
+// (qsim_dm_expectation).
 #pragma once
 
 #include <cstddef>

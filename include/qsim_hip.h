@@ -495,6 +495,24 @@ int qsim_dm_apply_channel(qsim_state* rho, int n_qubits, int type, int qubit, do
 int qsim_dm_diagonal(qsim_state* rho, int n_qubits, double* dst);          /* 2^n: Re rho_ii */
 int qsim_dm_init_pure(qsim_state* rho, int n_qubits, const double* psi);   /* rho = |psi><psi| */
 int qsim_dm_init_maximally_mixed(qsim_state* rho, int n_qubits);          /* rho = I / 2^n */
+/* Re Tr(rho H), H = sum_t c_t P_t over the n qubits (masks as in qsim_state_expectation), reduced
+ * on the device where rho lies (no reference counterpart).  Tr(rho P) = sum_{i < 2^n}
+ * rho[i][i ^ x] i^nY (-1)^popcount(i & z), nY = popcount(x & z): a string reads 2^n of the 4^n
+ * elements, strings with the same x mask the same ones.  All 2^n values of i are summed (no use of
+ * Hermiticity: the value is linear in whatever the buffer holds).  The element addresses are mapped
+ * through the state's current index-bit layout on the host, so the layout (qsim_state_perm), the
+ * current buffer and the amplitudes are left exactly as they are (the other readers of rho restore
+ * the identity layout first).  Partial sums are added in a fixed order: bitwise reproducible.  A
+ * mask bit >= n_qubits -> QSIM_ERR_OUT_OF_RANGE; count == 0 -> 0.0 with no launch.  Synchronises. */
+int qsim_dm_expectation(qsim_state* rho, int n_qubits, const qsim_pauli_term* terms, size_t count, double* out);
+/* Host-only (no GPU): what the lowering makes of these terms after duplicate strings are merged
+ * and zero coefficients dropped: groups (distinct x masks), rows (a group of more terms than one
+ * row's table holds takes several), kernel launches (all rows in one, up to the grid's limit of
+ * 65535 rows) and elements of rho read (groups x 2^n).  perm: the layout of the 2n index bits
+ * (logical -> physical, 2n entries; null: identity); anything but a permutation, or n_qubits
+ * outside [1, QSIM_DM_MAX_QUBITS] -> QSIM_ERR_INVALID_ARGUMENT. */
+int qsim_dm_expectation_plan(int n_qubits, const qsim_pauli_term* terms, size_t count, const int32_t* perm,
+                             int* groups, int* rows, int* launches, uint64_t* elements);
 
 /* ---- multi-GPU: state sharded by its high physical qubits, one process per GPU, RCCL ----
  * (the reference is single-GPU, README.md:361-367).  World size W = 2^g ranks;

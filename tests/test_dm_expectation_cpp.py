@@ -1,0 +1,31 @@
+"""The C++ density-matrix expectation tests (tests/cpp_dm_expectation/test_dm_expectation.cpp):
+DensityMatrix::expectation and DensityMatrixSimulator::expectation of the C++17 API, run as a child
+process (ordered before anything initialises the GPU here)."""
+import os
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CPP = os.path.join(ROOT, "tests", "cpp_dm_expectation")
+BIN = os.path.join(CPP, "build", "test_dm_expectation")
+
+
+def _build():
+    subprocess.run(["make", "-C", CPP], check=True, capture_output=True, text=True)
+    return BIN
+
+
+def test_cpp_dm_expectation_builds():
+    """CPU-side: the new methods compile with g++ alone and link the libraries."""
+    assert os.path.exists(_build())
+
+
+@pytest.mark.gpu
+@pytest.mark.subprocess
+def test_cpp_dm_expectation_suite():
+    exe = _build()
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    print(r.stdout[-4000:])
+    assert r.returncode == 0, r.stdout[-4000:] + r.stderr[-4000:]
+    assert " 0 failed" in r.stdout

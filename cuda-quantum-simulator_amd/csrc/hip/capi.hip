@@ -1960,6 +1960,105 @@ int qsim_state_gradient(qsim_state* s, const qsim_gate* gates, size_t count, con
     });
 }
 
+// ---- Pauli-string rotations and their adjoint gradients (pauli_rot.hip) ----
+static void check_pauli_masks(int n, const qsim_pauli_term* terms, size_t count, const char* what) {
+    const uint64_t valid = (1ull << n) - 1ull;
+    for (size_t t = 0; t < count; ++t)
+        if ((terms[t].x_mask | terms[t].z_mask) & ~valid)
+            fail(QSIM_ERR_OUT_OF_RANGE, std::string(what) + " acts on a qubit index out of range");
+}
+
+int qsim_state_apply_pauli_rotations(qsim_state* s, const qsim_pauli_term* rots, size_t count) {
+    return guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(rots || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        if (count == 0) return;
+        DeviceGuard dg(s->device);
+        share_flush(s);  // (pending gates of a run-sharing cycle; the layout may change with them)
+        // (the lowering checks every mask of the sequence: nothing of it is launched before)
+        const PauliRotPlan plan =
+            lower_pauli_rotations(s->n, rots, count, s->perm.empty() ? nullptr : s->perm.data());
+        s->basis = false;
+        launch_pauli_rotations(s->d, s->n, plan, s->expect_terms, s->stream, &s->timer);
+    });
+}
+
+int qsim_pauli_rotation_plan(int n_qubits, const qsim_pauli_term* rots, size_t count, const int32_t* perm,
+                             int* passes, int* launches) {
+    return guarded([&] {
+        QSIM_REQUIRE(rots || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        QSIM_REQUIRE(passes && launches, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        const PauliRotPlan plan = lower_pauli_rotations(n_qubits, rots, count, perm);
+        *passes = (int)plan.passes;
+        *launches = (int)plan.launches;
+    });
+}
+
+int qsim_pauli_gradient_plan(int n_qubits, const qsim_pauli_term* rots, size_t count,
+                             const qsim_pauli_term* terms, size_t nterms, const int32_t* perm, int* steps,
+                             int* apply_passes) {
+    return guarded([&] {
+        QSIM_REQUIRE(rots || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        QSIM_REQUIRE(terms || nterms == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        QSIM_REQUIRE(steps && apply_passes, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        const PauliRotPlan plan = lower_pauli_rotations(n_qubits, rots, count, perm);
+        const ExpectPlan aplan = lower_pauli_apply(n_qubits, terms, nterms, perm);
+        *steps = aplan.terms.empty() ? 0 : (int)plan.rots.size();  // (H == 0: no sweep)
+        *apply_passes = (int)aplan.launches;
+    });
+}
+
+int qsim_state_pauli_gradient(qsim_state* s, const qsim_pauli_term* rots, size_t count,
+                              const qsim_pauli_term* terms, size_t nterms, double* value, double* grad) {
+    int rc = guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(value, QSIM_ERR_INVALID_ARGUMENT, "null value");
+        QSIM_REQUIRE(grad || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gradient");
+        QSIM_REQUIRE(rots || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        QSIM_REQUIRE(terms || nterms == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        // (the observable before the sequence is applied; the sequence's masks: by that call)
+        check_pauli_masks(s->n, terms, nterms, "Pauli term");
+    });
+    if (rc != QSIM_OK) return rc;
+    // The forward pass is qsim_state_apply_pauli_rotations itself: the state ends exactly as that
+    // call alone leaves it, and nothing below writes to it.
+    if ((rc = qsim_state_apply_pauli_rotations(s, rots, count)) != QSIM_OK) return rc;
+    return guarded([&] {
+        DeviceGuard dg(s->device);
+        share_flush(s);  // (count == 0: nothing above has flushed)
+        const int n = s->n;
+        *value = 0.0;
+        for (size_t k = 0; k < count; ++k) grad[k] = 0.0;
+        const int* perm = s->perm.empty() ? nullptr : s->perm.data();
+        const ExpectPlan eplan = lower_expectation(n, terms, nterms, perm);
+        if (eplan.terms.empty()) {  // H = 0 (no terms, or every coefficient cancels): no sweep
+            QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+            return;
+        }
+        // (the work states first: a failed allocation leaves nothing queued)
+        GradWork* wp = count > 0 ? &ensure_grad(s, count) : nullptr;
+        launch_expectation(s->d, n, 1, eplan, s->expect_terms, s->d_partials, s->d_result, s->stream, &s->timer);
+        QSIM_HIPCHK(hipMemcpyAsync(value, s->d_result, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        if (!wp) {  // no rotation: the value alone
+            QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+            return;
+        }
+        GradWork& w = *wp;
+        // phi: the state where it lies (same layout); lambda = H phi under that layout
+        QSIM_HIPCHK(hipMemcpyAsync(w.phi, s->d, sizeof(double2) << n, hipMemcpyDeviceToDevice, s->stream));
+        launch_pauli_apply(s->d, w.lam, n, lower_pauli_apply(n, terms, nterms, perm), w.terms, s->stream, &s->timer);
+        const PauliRotPlan plan = lower_pauli_rotations(n, rots, count, perm);
+        // every rotation its own step, last to first; the first rotation undoes nothing
+        for (size_t k = count; k-- > 0;)
+            launch_pauli_adjoint_step(w.phi, w.lam, n, plan.rots[k], k > 0, s->d_partials, w.d_out + k, s->stream,
+                                      &s->timer);
+        QSIM_HIPCHK(hipMemcpyAsync(grad, w.d_out, count * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+    });
+}
+
 int qsim_state_collapse(qsim_state* s, int bit, int result, double scale) {
     return guarded([&] {
         check_state(s);

@@ -557,6 +557,11 @@ ExpectPlan lower_expectation(int n, const qsim_pauli_term* terms, size_t count, 
 // weights start at 0.
 ExpectPlan lower_pauli_terms(int n, const qsim_pauli_term* terms, size_t count, const int* perm,
                              const std::function<void(uint64_t, uint64_t, double, ExpectTerm&)>& weight);
+// The two host steps every Pauli lowering starts with (expect.hip): n in [1, 63] and perm (null:
+// identity) a permutation of 0..n-1, else Error (invalid argument); a logical mask at its physical
+// positions under perm.
+void check_qubit_perm(int n, const int* perm);
+uint64_t mask_to_physical(uint64_t m, int n, const int* perm);
 size_t expect_chunks(uint64_t batch);  // partials per trajectory a launch may write
 // d_out[t] = the plan's sum on trajectory t of st ([batch][2^n]); terms: the owner's device copy of
 // the term table (uploaded here), d_partials: batch * expect_chunks(batch) doubles.  Nothing is
@@ -669,6 +674,36 @@ void launch_adjoint_step(double2* phi, double2* lam, int n, const Generator& g, 
 // `count` device terms at d_terms; first: the first launch writes dst, later ones accumulate.
 void launch_pauli_apply_group(const double2* src, double2* dst, int n, uint64_t x, const ExpectTerm* d_terms,
                               size_t count, bool first, hipStream_t s, Timer* tm);
+
+// Pauli-string rotations exp(-i theta/2 P) (pauli_rot.hip).  A rotation under the state's layout:
+// physical masks (the convention of qsim_pauli_term) and the angle.
+struct PauliRot {
+    uint64_t x, z;
+    double theta;
+};
+// A sequence in application order.  passes: streaming passes over the state (one per x != 0
+// rotation, one per maximal run of consecutive x == 0 rotations); launches: kernel launches (a run
+// of more than kExpectTerms rotations takes several).
+struct PauliRotPlan {
+    std::vector<PauliRot> rots;
+    size_t passes = 0, launches = 0;
+};
+// Maps the masks from logical to physical bits through perm (null: identity); nothing is merged or
+// reordered.  Throws Error: a null list or a perm that is no permutation (invalid argument), a
+// mask bit >= n anywhere in the sequence (out of range).
+PauliRotPlan lower_pauli_rotations(int n, const qsim_pauli_term* rots, size_t count, const int* perm);
+uint64_t pauli_stream_blocks();  // QSIM_PAULI_BLOCKS (default 65536), read at every call
+// st <- exp(-i theta/2 P) st in place, x != 0: one thread per pair (i, i ^ x).  Asynchronous.
+void launch_pauli_rot(double2* st, int n, const PauliRot& r, hipStream_t s, Timer* tm);
+// st[i] *= exp(-i/2 sum_t theta_t (-1)^popcount(i & z_t)) over `count` device terms (z, cr = theta),
+// one launch per kExpectTerms of them.
+void launch_pauli_phase(double2* st, int n, const ExpectTerm* d_terms, size_t count, hipStream_t s, Timer* tm);
+// The whole plan on st; terms: the owner's device copy of the x == 0 runs' tables (one upload).
+void launch_pauli_rotations(double2* st, int n, const PauliRotPlan& plan, DevBuf& terms, hipStream_t s, Timer* tm);
+// *d_out = Im <lam| P |phi>, then (apply) exp(+i theta/2 P) on both states, in one launch; without
+// apply nothing is stored: the bra-ket alone.  d_partials: expect_chunks(1) doubles.
+void launch_pauli_adjoint_step(double2* phi, double2* lam, int n, const PauliRot& r, bool apply, double* d_partials,
+                               double* d_out, hipStream_t s, Timer* tm);
 
 // Adjoint-method gradients on a sharded state (dist_adjoint.hip; the transfers, the inverted
 // segments and the collectives around it: dist.hip).

@@ -31,26 +31,31 @@
 
 namespace qsim_hip {
 
+void check_qubit_perm(int n, const int* perm) {
+    if (n < 1 || n > 63) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+    if (!perm) return;
+    uint64_t seen = 0;
+    for (int q = 0; q < n; ++q) {
+        if (perm[q] < 0 || perm[q] >= n || (seen >> perm[q] & 1ull))
+            fail(QSIM_ERR_INVALID_ARGUMENT, "perm is not a permutation of the qubits");
+        seen |= 1ull << perm[q];
+    }
+}
+
+uint64_t mask_to_physical(uint64_t m, int n, const int* perm) {
+    if (!perm) return m;
+    uint64_t p = 0;
+    for (int q = 0; q < n; ++q)
+        if (m >> q & 1ull) p |= 1ull << perm[q];
+    return p;
+}
+
 ExpectPlan lower_pauli_terms(int n, const qsim_pauli_term* terms, size_t count, const int* perm,
                              const std::function<void(uint64_t, uint64_t, double, ExpectTerm&)>& weight) {
-    if (n < 1 || n > 63) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+    check_qubit_perm(n, perm);
     if (count && !terms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
-    if (perm) {
-        uint64_t seen = 0;
-        for (int q = 0; q < n; ++q) {
-            if (perm[q] < 0 || perm[q] >= n || (seen >> perm[q] & 1ull))
-                fail(QSIM_ERR_INVALID_ARGUMENT, "perm is not a permutation of the qubits");
-            seen |= 1ull << perm[q];
-        }
-    }
     const uint64_t valid = (1ull << n) - 1ull;
-    auto to_phys = [&](uint64_t m) {
-        if (!perm) return m;
-        uint64_t p = 0;
-        for (int q = 0; q < n; ++q)
-            if (m >> q & 1ull) p |= 1ull << perm[q];
-        return p;
-    };
+    auto to_phys = [&](uint64_t m) { return mask_to_physical(m, n, perm); };
     // merged coefficients keyed by the physical (x, z): iteration order is by x, then z
     std::map<std::pair<uint64_t, uint64_t>, double> merged;
     for (size_t t = 0; t < count; ++t) {

@@ -41,6 +41,31 @@ PauliSum& PauliSum::add(double coeff, const std::vector<std::pair<int, char>>& f
     return *this;
 }
 
+PauliSum trotter_sequence(const PauliSum& H, double time, int steps, int order) {
+    if (steps < 1) throw std::invalid_argument("steps must be at least 1");
+    if (order != 1 && order != 2) throw std::invalid_argument("order must be 1 or 2");
+    PauliSum seq(H.getNumQubits());
+    const std::vector<PauliSum::Term>& terms = H.terms();
+    const size_t T = terms.size();
+    auto rot = [&](size_t t, double scale) {
+        seq.terms_.push_back(
+            PauliSum::Term{terms[t].x_mask, terms[t].z_mask, scale * (2.0 * terms[t].coeff * time / steps)});
+    };
+    if (order == 1 || T <= 1) {
+        for (int s = 0; s < steps; ++s)
+            for (size_t t = 0; t < T; ++t) rot(t, 1.0);
+        return seq;
+    }
+    for (int s = 0; s < steps; ++s) {
+        rot(0, s == 0 ? 0.5 : 1.0);  // (step s - 1 ended with the other half)
+        for (size_t t = 1; t + 1 < T; ++t) rot(t, 0.5);
+        rot(T - 1, 1.0);
+        for (size_t t = T - 1; t-- > 1;) rot(t, 0.5);
+    }
+    rot(0, 0.5);
+    return seq;
+}
+
 static std::vector<qsim_pauli_term> toAbi(const PauliSum& p, int num_qubits) {
     if (p.getNumQubits() != num_qubits)
         throw std::invalid_argument("Observable qubit count doesn't match simulator");
@@ -79,6 +104,34 @@ Gradient Simulator::gradient(const Circuit& circuit, const PauliSum& observable,
     check(qsim_state_gradient(state_.handle(), gates.data(), gates.size(), terms.data(), terms.size(),
                               mode == RunMode::Fused ? QSIM_RUN_FUSED : QSIM_RUN_PER_GATE, &g.value,
                               g.gradient.data()));
+    return g;
+}
+
+void StateVector::applyPauliRotation(const std::vector<std::pair<int, char>>& factors, double theta) {
+    applyPauliRotations(PauliSum(num_qubits_).add(theta, factors));
+}
+
+void StateVector::applyPauliRotations(const PauliSum& seq) {
+    const std::vector<qsim_pauli_term> rots = toAbi(seq, num_qubits_);
+    check(qsim_state_apply_pauli_rotations(h_, rots.data(), rots.size()));
+}
+
+void Simulator::applyPauliRotation(const std::vector<std::pair<int, char>>& factors, double theta) {
+    state_.applyPauliRotation(factors, theta);
+}
+
+void Simulator::applyPauliRotations(const PauliSum& seq) { state_.applyPauliRotations(seq); }
+
+void Simulator::evolve(const PauliSum& H, double time, int steps, int order) {
+    state_.applyPauliRotations(trotter_sequence(H, time, steps, order));
+}
+
+Gradient Simulator::pauliGradient(const PauliSum& seq, const PauliSum& observable) {
+    const std::vector<qsim_pauli_term> rots = toAbi(seq, state_.getNumQubits());
+    const std::vector<qsim_pauli_term> terms = toAbi(observable, state_.getNumQubits());
+    Gradient g{0.0, std::vector<double>(rots.size(), 0.0)};
+    check(qsim_state_pauli_gradient(state_.handle(), rots.data(), rots.size(), terms.data(), terms.size(), &g.value,
+                                    g.gradient.data()));
     return g;
 }
 

@@ -10,7 +10,7 @@ from .circuit import (Circuit, GateOp, GateType, MAX_QUBITS, MIN_QUBITS, createB
 from .simulator import (BatchedGateSet, BatchedNoise, BatchedSimulator, NoiseChannel, NoiseModel, NoiseType,
                         NoisySimulator, RunMode, Simulator, StateVector, device_count, device_info,
                         set_device)
-from .observable import PauliSum
+from .observable import PauliSum, trotter_sequence
 from .density import DensityMatrix, DensityMatrixSimulator
 
 __all__ = [
@@ -19,5 +19,5 @@ __all__ = [
     "createGHZCircuit", "createRandomCircuit", "createRandomHCCircuit",
     "createScalingBenchmarkCircuit", "is_valid_qubit_count", "BatchedGateSet", "BatchedNoise",
     "BatchedSimulator", "NoiseChannel", "NoiseModel", "NoiseType", "NoisySimulator", "RunMode", "Simulator",
-    "StateVector", "PauliSum", "device_count", "device_info", "set_device",
+    "StateVector", "PauliSum", "trotter_sequence", "device_count", "device_info", "set_device",
 ]

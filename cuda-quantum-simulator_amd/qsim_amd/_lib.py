@@ -148,6 +148,13 @@ _sig(hip, "qsim_gradient_plan", [c_int, POINTER(qsim_gate), c_size_t, POINTER(qs
 _sig(hip, "qsim_state_gradient", [_P, POINTER(qsim_gate), c_size_t, POINTER(qsim_pauli_term), c_size_t, c_int,
                                   POINTER(c_double), POINTER(c_double)])
 _sig(hip, "qsim_state_gradient_release", [_P])
+_sig(hip, "qsim_state_apply_pauli_rotations", [_P, POINTER(qsim_pauli_term), c_size_t])
+_sig(hip, "qsim_pauli_rotation_plan", [c_int, POINTER(qsim_pauli_term), c_size_t, POINTER(c_int32), POINTER(c_int),
+                                       POINTER(c_int)])
+_sig(hip, "qsim_state_pauli_gradient", [_P, POINTER(qsim_pauli_term), c_size_t, POINTER(qsim_pauli_term), c_size_t,
+                                        POINTER(c_double), POINTER(c_double)])
+_sig(hip, "qsim_pauli_gradient_plan", [c_int, POINTER(qsim_pauli_term), c_size_t, POINTER(qsim_pauli_term), c_size_t,
+                                       POINTER(c_int32), POINTER(c_int), POINTER(c_int)])
 _sig(hip, "qsim_state_profile", [_P, c_int])
 _sig(hip, "qsim_state_profile_count", [_P, POINTER(c_int)])
 _sig(hip, "qsim_state_profile_get", [_P, c_int, c_char_p, c_size_t, POINTER(c_double),

@@ -182,6 +182,40 @@ def gradient_plan(circuit: Circuit, observable):
     return p.value, s.value, a.value
 
 
+def _perm_arg(n: int, perm):
+    if perm is None:
+        return None
+    if len(perm) != n:
+        raise ValueError("perm needs one entry per qubit")
+    return (ctypes.c_int32 * n)(*[int(p) for p in perm])
+
+
+def pauli_rotation_plan(seq, perm=None):
+    """(passes over the state, kernel launches) applyPauliRotations(seq) makes under the qubit
+    layout perm (logical -> physical; None: identity): one pass per rotation with an X or Y factor,
+    one per maximal run of consecutive Z/I-only rotations, one launch per 256 rotations of a run
+    (qsim_pauli_rotation_plan, host only)."""
+    n = seq.getNumQubits()
+    rots, count = seq.to_abi(n)
+    p, l = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.hip.qsim_pauli_rotation_plan(n, rots, count, _perm_arg(n, perm), ctypes.byref(p),
+                                                 ctypes.byref(l)))
+    return p.value, l.value
+
+
+def pauli_gradient_plan(seq, observable, perm=None):
+    """(steps of the backward sweep, Pauli-sum apply passes) of Simulator.pauliGradient under the
+    qubit layout perm (qsim_pauli_gradient_plan, host only): every rotation its own step, no step
+    when H = 0."""
+    n = seq.getNumQubits()
+    rots, count = seq.to_abi(n)
+    terms, nterms = observable.to_abi(n)
+    s, a = ctypes.c_int(0), ctypes.c_int(0)
+    _lib.check(_lib.hip.qsim_pauli_gradient_plan(n, rots, count, terms, nterms, _perm_arg(n, perm),
+                                                 ctypes.byref(s), ctypes.byref(a)))
+    return s.value, a.value
+
+
 def jit_build_relayout(circuit: Circuit) -> int:
     """Compile the circuit's relayout plan (qsim_jit_build_relayout, hipRTC for gfx950, no GPU
     needed); returns the code-object size in bytes."""

@@ -17,6 +17,7 @@ import numpy as np
 
 from . import _lib
 from .circuit import Circuit, GateOp, is_valid_qubit_count, MAX_QUBITS, MIN_QUBITS
+from .observable import PauliSum, trotter_sequence
 
 _c = ctypes
 
@@ -164,6 +165,22 @@ class StateVector:
         state's qubit layout.  ValueError when dst is self or of another size."""
         terms, count = observable.to_abi(self._n)
         _lib.check(_lib.hip.qsim_state_apply_pauli_sum(self._h, dst._h, terms, count))
+
+    def applyPauliRotation(self, factors, theta: float) -> None:
+        """exp(-i theta/2 P) in place, P the product of the factors {qubit: 'X' | 'Y' | 'Z'} (as
+        PauliSum.add takes them; none: the global phase exp(-i theta/2)): one streaming pass over
+        the state whatever the string's weight.  IndexError on a bad qubit, before anything is
+        applied."""
+        self.applyPauliRotations(PauliSum(self._n).add(theta, factors))
+
+    def applyPauliRotations(self, seq) -> None:
+        """A PauliSum read as an ordered sequence: term t is exp(-i coeff_t/2 P_t), applied in
+        add() order where the state lies, no layout restore (qsim_state_apply_pauli_rotations; no
+        reference counterpart).  Every rotation with an X or Y factor is one pass; a run of
+        consecutive Z/I-only rotations shares one.  Asynchronous.  ValueError on a qubit-count
+        mismatch."""
+        rots, count = seq.to_abi(self._n)
+        _lib.check(_lib.hip.qsim_state_apply_pauli_rotations(self._h, rots, count))
 
     def innerProduct(self, other: "StateVector") -> complex:
         """<self|other> by a fixed-order device reduction (qsim_state_inner_product)."""
@@ -378,6 +395,38 @@ class Simulator:
         _lib.check(_lib.hip.qsim_state_gradient(self._state.handle, arr, cnt, terms, nterms, int(mode),
                                                 _c.byref(value), grad.ctypes.data_as(_c.POINTER(_c.c_double))))
         return value.value, grad[:cnt]
+
+    # Pauli-string rotations (no reference counterpart): StateVector.applyPauliRotation(s)
+    def applyPauliRotation(self, factors, theta: float) -> None:
+        self._state.applyPauliRotation(factors, theta)
+
+    def applyPauliRotations(self, seq) -> None: self._state.applyPauliRotations(seq)
+
+    def evolve(self, H, time: float, steps: int = 1, order: int = 1) -> None:
+        """The Trotter product for exp(-i H time) on the state as it is: nothing but
+        applyPauliRotations(trotter_sequence(H, time, steps, order)) (observable.trotter_sequence
+        defines both orders).  ValueError when steps < 1, order is not 1 or 2 or the qubit counts
+        differ."""
+        self.applyPauliRotations(trotter_sequence(H, time, steps, order))
+
+    def pauliGradient(self, seq, observable):
+        """(value, gradient): applies the rotation sequence `seq` (a PauliSum read in add() order,
+        as applyPauliRotations does) to the state as it is, then <psi|H|psi> and its derivative
+        with respect to the angle of every rotation (numpy array, one entry per term of seq) by
+        the adjoint method: one backward sweep on the device, one fused pass over two work states
+        per rotation (qsim_state_pauli_gradient).  The state is left as applyPauliRotations(seq)
+        leaves it.  The angles are independent parameters here: a parameter shared between
+        rotations (a QAOA gamma, a Trotter time) is the caller's chain rule over the returned
+        gradient, d E / d gamma = sum_k grad[k] d theta_k / d gamma.  The work states are those
+        of gradient() (releaseGradientBuffers frees them)."""
+        n = self._state.getNumQubits()
+        rots, count = seq.to_abi(n)
+        terms, nterms = observable.to_abi(n)
+        value = _c.c_double()
+        grad = np.zeros(max(1, count), dtype=np.float64)
+        _lib.check(_lib.hip.qsim_state_pauli_gradient(self._state.handle, rots, count, terms, nterms,
+                                                      _c.byref(value), grad.ctypes.data_as(_c.POINTER(_c.c_double))))
+        return value.value, grad[:count]
 
     def releaseGradientBuffers(self) -> None:
         """Free the two work states gradient() keeps on the state between calls."""

@@ -58,6 +58,20 @@ public:
     // reference counterpart.
     Gradient gradient(const Circuit& circuit, const PauliSum& observable, RunMode mode = RunMode::Fused);
     void releaseGradientBuffers();  // free the two work states gradient() keeps between calls
+    // Pauli-string rotations (no reference counterpart): StateVector::applyPauliRotation(s).
+    void applyPauliRotation(const std::vector<std::pair<int, char>>& factors, double theta);
+    void applyPauliRotations(const PauliSum& seq);
+    // The Trotter product for exp(-i H time) on the state as it is: nothing but
+    // applyPauliRotations(trotter_sequence(H, time, steps, order)) (Observable.hpp defines both
+    // orders).  std::invalid_argument when steps < 1, order is not 1 or 2 or the qubit counts differ.
+    void evolve(const PauliSum& H, double time, int steps = 1, int order = 1);
+    // Applies the rotation sequence `seq` (a PauliSum read in add() order) to the state as it is,
+    // then returns <psi|H|psi> and its derivative with respect to the angle of every rotation (one
+    // entry per term of seq) by the adjoint method: one backward sweep on the device, one fused
+    // pass over two work states per rotation (qsim_state_pauli_gradient).  The state is left as
+    // applyPauliRotations(seq) leaves it.  The angles are independent parameters: a parameter
+    // shared between rotations (a QAOA gamma) is the caller's chain rule over the gradient.
+    Gradient pauliGradient(const PauliSum& seq, const PauliSum& observable);
 
     int getNumQubits() const { return state_.getNumQubits(); }
     size_t getStateSize() const { return state_.getSize(); }

@@ -9,6 +9,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <random>
+#include <utility>
 #include <vector>
 
 struct qsim_state;
@@ -68,6 +69,15 @@ public:
     // dst = H |this> out of place on the device (qsim_state_apply_pauli_sum); dst takes this
     // state's qubit layout.  std::invalid_argument on a qubit-count mismatch or &dst == this.
     void applyPauliSum(const PauliSum& observable, StateVector& dst) const;
+    // exp(-i theta/2 P) in place, P the product of the factors (qubit, 'X' | 'Y' | 'Z') (none: the
+    // global phase exp(-i theta/2)): one streaming pass over the state whatever the string's
+    // weight.  std::out_of_range on a bad qubit, before anything is applied.
+    void applyPauliRotation(const std::vector<std::pair<int, char>>& factors, double theta);
+    // A PauliSum read as an ordered sequence: term t is exp(-i coeff_t/2 P_t), applied in add()
+    // order where the state lies, no layout restore (qsim_state_apply_pauli_rotations; no reference
+    // counterpart).  A run of consecutive Z/I-only rotations shares one pass.  Asynchronous.
+    // std::invalid_argument on a qubit-count mismatch.
+    void applyPauliRotations(const PauliSum& seq);
     // <this|other> by a fixed-order device reduction (qsim_state_inner_product): bitwise
     // reproducible; innerProduct(*this) is the norm.  std::invalid_argument on a size mismatch.
     std::complex<double> innerProduct(const StateVector& other) const;

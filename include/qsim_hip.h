@@ -361,6 +361,47 @@ int qsim_state_gradient(qsim_state* s, const qsim_gate* gates, size_t count, con
                         size_t nterms, int flags, double* value, double* grad);
 int qsim_state_gradient_release(qsim_state* s); /* free the gradient work buffers now */
 
+/* ---- Pauli-string rotations exp(-i theta/2 P) and their adjoint gradients (no reference
+ * counterpart) ----
+ * A rotation is a qsim_pauli_term whose coeff is the angle theta in radians; a sequence is an array
+ * of them in application order.  Whatever its weight, a rotation with an X or Y factor is ONE
+ * streaming pass over the state (amplitude i pairs with i ^ x_mask); a maximal run of consecutive
+ * Z/I-only rotations (they commute; the identity string, a global phase, included) is one pass,
+ * one kernel launch per 256 rotations of the run.  Nothing else is reordered or merged.
+ * Behaves as qsim_apply_gate: pending gates of a run-sharing cycle are flushed first, the masks
+ * are mapped through the state's current qubit layout on the host, the layout is neither restored
+ * nor re-decided, and the figures of the last fused run stay.  Asynchronous.  count == 0 launches
+ * nothing.  A mask bit >= n anywhere in the sequence -> QSIM_ERR_OUT_OF_RANGE before the first
+ * launch; null rots with count > 0 -> QSIM_ERR_INVALID_ARGUMENT.  QSIM_PAULI_BLOCKS (1..65536,
+ * default 65536, read at every call) caps the work-groups of the two streaming kernels; the
+ * amplitudes do not depend on it. */
+int qsim_state_apply_pauli_rotations(qsim_state* s, const qsim_pauli_term* rots, size_t count);
+/* Host-only (no GPU): the passes over the state and the kernel launches the call above makes for
+ * this sequence under the qubit layout perm (logical -> physical, n entries; null: identity).
+ * The same error codes; a perm that is no permutation -> QSIM_ERR_INVALID_ARGUMENT. */
+int qsim_pauli_rotation_plan(int n_qubits, const qsim_pauli_term* rots, size_t count, const int32_t* perm,
+                             int* passes, int* launches);
+/* Applies the sequence to the state as qsim_state_apply_pauli_rotations does, then
+ * *value = <psi|H|psi> and grad[k] = dE/dtheta_k for k < count, by the adjoint method: one backward
+ * sweep over the two work states of qsim_state_gradient (the same buffers, counted by
+ * qsim_state_memory_bytes, freed by qsim_state_gradient_release), one fused launch per rotation
+ * (Im <lambda|P|phi>, then exp(+i theta/2 P) on both work states: 64 B per amplitude); the last
+ * step of the sweep, the sequence's first rotation, is the bra-ket alone.  Every rotation takes
+ * its own step: Z-only runs are not merged in the sweep.  The sweep never writes the state: it
+ * ends exactly as qsim_state_apply_pauli_rotations alone leaves it.  nterms == 0 or H == 0:
+ * *value = 0, all-zero gradient, no sweep; count == 0: *value = <H> of the state as it is.  A
+ * parameter shared between rotations is the caller's chain rule over grad.  Error codes and the
+ * out-of-memory behaviour are those of qsim_state_gradient (every argument is checked before the
+ * sequence is applied).  Bitwise reproducible.  Synchronises. */
+int qsim_state_pauli_gradient(qsim_state* s, const qsim_pauli_term* rots, size_t count,
+                              const qsim_pauli_term* terms, size_t nterms, double* value, double* grad);
+/* Host-only: what qsim_state_pauli_gradient would do under the layout perm (null: identity): the
+ * steps of the backward sweep (count; 0 when H == 0) and the passes over the state of the
+ * Pauli-sum apply.  The same error codes. */
+int qsim_pauli_gradient_plan(int n_qubits, const qsim_pauli_term* rots, size_t count,
+                             const qsim_pauli_term* terms, size_t nterms, const int32_t* perm, int* steps,
+                             int* apply_passes);
+
 /* ---- timing (bench / profiling) ---- */
 /* Enable per-launch HIP-event timing on the state's stream; kernels are attributed by name. */
 int qsim_state_profile(qsim_state* s, int enable);

@@ -17,7 +17,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <vector>
 
 #include "device_ops.hpp"
@@ -59,9 +58,13 @@ Generator gate_generator(const qsim_gate& g) {
 
 // QSIM_ADJOINT_FUSED (default 1; read at every call, so a test or a benchmark runs both paths in
 // one process): 0 composes a parameterised step from braket and two per-gate launches.
-bool adjoint_fused_on() {
-    const char* e = std::getenv("QSIM_ADJOINT_FUSED");
-    return e == nullptr || std::atoi(e) != 0;
+bool adjoint_fused_on() { return env_switch("QSIM_ADJOINT_FUSED", true); }
+
+void check_gradient_args(int n, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms, size_t nterms) {
+    if (!gates && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gate list");
+    if (!terms && nterms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
+    for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n);
+    check_pauli_masks(n, terms, nterms, "Pauli term");
 }
 
 // The terms of dst = H src: (P src)[i] = i^nY (-1)^popcount((i ^ x) & z) src[i ^ x].  The sign is
@@ -83,14 +86,6 @@ namespace {
 // conj(a) g
 __device__ __forceinline__ double2 cjmul(double2 a, double2 g) {
     return make_double2(a.x * g.x + a.y * g.y, a.x * g.y - a.y * g.x);
-}
-
-// The 256 threads' values added in a fixed order; the total is returned in thread 0.
-__device__ __forceinline__ double block_sum(double acc, double* wsum) {
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
 }
 
 // Pair k of the active subspace: zeros inserted at the ascending positions f0 (< f1), the control
@@ -134,14 +129,11 @@ __global__ __launch_bounds__(256) void k_pauli_apply(const double2* __restrict__
     const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += step) {
         const double2 v = src[i ^ x];
-        double wr = 0.0, wi = 0.0;
-        for (int t = 0; t < nterms; ++t) {  // (same LDS address in every lane: broadcast reads)
-            const ExpectTerm e = tab[t];
-            const bool neg = __popcll(i & e.z) & 1;
-            wr += neg ? -e.cr : e.cr;
-            wi += neg ? -e.ci : e.ci;
-        }
-        double2 o = make_double2(wr * v.x - wi * v.y, wr * v.y + wi * v.x);
+        double wr, wi;
+        term_weight<true>(tab, nterms, i, wr, wi);
+        // (explicit fma: which product of a sum of two is rounded on its own is otherwise the
+        // compiler's choice, and the gradients' last bit with it)
+        double2 o = make_double2(fma(wr, v.x, -(wi * v.y)), fma(wi, v.x, wr * v.y));
         if (ACC) {
             const double2 d = dst[i];
             o.x += d.x;

@@ -1786,15 +1786,33 @@ static void grad_apply_segment(qsim_state* s, GradWork& w, const std::vector<Op>
     }
 }
 
-static void check_gradient_args(int n, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms,
-                                size_t nterms) {
-    QSIM_REQUIRE(gates || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gate list");
-    QSIM_REQUIRE(terms || nterms == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
-    for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n);
-    const uint64_t valid = (1ull << n) - 1ull;
-    for (size_t t = 0; t < nterms; ++t)
-        if ((terms[t].x_mask | terms[t].z_mask) & ~valid)
-            fail(QSIM_ERR_OUT_OF_RANGE, "Pauli term acts on a qubit index out of range");
+// What the two gradient entry points below do once the forward pass has run: the outputs zeroed,
+// *value = <psi|H|psi> queued and, with `sweep` (there is something to differentiate), the work
+// states of the backward sweep queued as well: phi = a copy of the state where it lies, lambda =
+// H phi under that layout.  Returns them, or null when the call is already complete (H = 0, or no
+// sweep): the stream is then drained.
+static GradWork* gradient_prologue(qsim_state* s, const qsim_pauli_term* terms, size_t nterms, size_t count,
+                                   bool sweep, double* value, double* grad) {
+    const int n = s->n;
+    *value = 0.0;
+    for (size_t k = 0; k < count; ++k) grad[k] = 0.0;
+    const int* perm = s->perm.empty() ? nullptr : s->perm.data();
+    const ExpectPlan eplan = lower_expectation(n, terms, nterms, perm);
+    if (eplan.terms.empty()) {  // H = 0 (no terms, or every coefficient cancels): no sweep
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+        return nullptr;
+    }
+    // (the work states first: a failed allocation leaves nothing queued)
+    GradWork* w = sweep ? &ensure_grad(s, count) : nullptr;
+    launch_expectation(s->d, n, 1, eplan, s->expect_terms, s->d_partials, s->d_result, s->stream, &s->timer);
+    QSIM_HIPCHK(hipMemcpyAsync(value, s->d_result, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (!w) {  // the value alone
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+        return nullptr;
+    }
+    QSIM_HIPCHK(hipMemcpyAsync(w->phi, s->d, sizeof(double2) << n, hipMemcpyDeviceToDevice, s->stream));
+    launch_pauli_apply(s->d, w->lam, n, lower_pauli_apply(n, terms, nterms, perm), w->terms, s->stream, &s->timer);
+    return w;
 }
 
 int qsim_gate_inverse(const qsim_gate* g, qsim_gate* out) {
@@ -1906,29 +1924,12 @@ int qsim_state_gradient(qsim_state* s, const qsim_gate* gates, size_t count, con
     return guarded([&] {
         DeviceGuard dg(s->device);
         const int n = s->n;
-        *value = 0.0;
-        for (size_t k = 0; k < count; ++k) grad[k] = 0.0;
-        const int* perm = s->perm.empty() ? nullptr : s->perm.data();
-        const ExpectPlan eplan = lower_expectation(n, terms, nterms, perm);
         size_t first_param = count;
         for (size_t k = count; k-- > 0;)
             if (gate_is_parameterised(gates[k].type)) first_param = k;
-        if (eplan.terms.empty()) {  // H = 0 (no terms, or every coefficient cancels): no sweep
-            QSIM_HIPCHK(hipStreamSynchronize(s->stream));
-            return;
-        }
-        // (the work states first: a failed allocation leaves nothing queued)
-        GradWork* wp = first_param < count ? &ensure_grad(s, count) : nullptr;
-        launch_expectation(s->d, n, 1, eplan, s->expect_terms, s->d_partials, s->d_result, s->stream, &s->timer);
-        QSIM_HIPCHK(hipMemcpyAsync(value, s->d_result, sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        if (!wp) {  // no parameter: the value alone
-            QSIM_HIPCHK(hipStreamSynchronize(s->stream));
-            return;
-        }
+        GradWork* wp = gradient_prologue(s, terms, nterms, count, first_param < count, value, grad);
+        if (!wp) return;  // H = 0, or no parameter: the value alone
         GradWork& w = *wp;
-        // phi: the state where it lies (same layout); lambda = H phi under that layout
-        QSIM_HIPCHK(hipMemcpyAsync(w.phi, s->d, sizeof(double2) << n, hipMemcpyDeviceToDevice, s->stream));
-        launch_pauli_apply(s->d, w.lam, n, lower_pauli_apply(n, terms, nterms, perm), w.terms, s->stream, &s->timer);
         QSIM_HIPCHK(hipMemsetAsync(w.d_out, 0, count * sizeof(double), s->stream));
         const int th = s->tile_h >= 0 ? s->tile_h : tile_height_for(n);
         const TileHeightScope tile_h(th, tile_rb_for(n, th));  // the segments' plans
@@ -1961,13 +1962,6 @@ int qsim_state_gradient(qsim_state* s, const qsim_gate* gates, size_t count, con
 }
 
 // ---- Pauli-string rotations and their adjoint gradients (pauli_rot.hip) ----
-static void check_pauli_masks(int n, const qsim_pauli_term* terms, size_t count, const char* what) {
-    const uint64_t valid = (1ull << n) - 1ull;
-    for (size_t t = 0; t < count; ++t)
-        if ((terms[t].x_mask | terms[t].z_mask) & ~valid)
-            fail(QSIM_ERR_OUT_OF_RANGE, std::string(what) + " acts on a qubit index out of range");
-}
-
 int qsim_state_apply_pauli_rotations(qsim_state* s, const qsim_pauli_term* rots, size_t count) {
     return guarded([&] {
         check_state(s);
@@ -2029,27 +2023,11 @@ int qsim_state_pauli_gradient(qsim_state* s, const qsim_pauli_term* rots, size_t
         DeviceGuard dg(s->device);
         share_flush(s);  // (count == 0: nothing above has flushed)
         const int n = s->n;
-        *value = 0.0;
-        for (size_t k = 0; k < count; ++k) grad[k] = 0.0;
-        const int* perm = s->perm.empty() ? nullptr : s->perm.data();
-        const ExpectPlan eplan = lower_expectation(n, terms, nterms, perm);
-        if (eplan.terms.empty()) {  // H = 0 (no terms, or every coefficient cancels): no sweep
-            QSIM_HIPCHK(hipStreamSynchronize(s->stream));
-            return;
-        }
-        // (the work states first: a failed allocation leaves nothing queued)
-        GradWork* wp = count > 0 ? &ensure_grad(s, count) : nullptr;
-        launch_expectation(s->d, n, 1, eplan, s->expect_terms, s->d_partials, s->d_result, s->stream, &s->timer);
-        QSIM_HIPCHK(hipMemcpyAsync(value, s->d_result, sizeof(double), hipMemcpyDeviceToHost, s->stream));
-        if (!wp) {  // no rotation: the value alone
-            QSIM_HIPCHK(hipStreamSynchronize(s->stream));
-            return;
-        }
+        GradWork* wp = gradient_prologue(s, terms, nterms, count, count > 0, value, grad);
+        if (!wp) return;  // H = 0, or no rotation: the value alone
         GradWork& w = *wp;
-        // phi: the state where it lies (same layout); lambda = H phi under that layout
-        QSIM_HIPCHK(hipMemcpyAsync(w.phi, s->d, sizeof(double2) << n, hipMemcpyDeviceToDevice, s->stream));
-        launch_pauli_apply(s->d, w.lam, n, lower_pauli_apply(n, terms, nterms, perm), w.terms, s->stream, &s->timer);
-        const PauliRotPlan plan = lower_pauli_rotations(n, rots, count, perm);
+        const PauliRotPlan plan =
+            lower_pauli_rotations(n, rots, count, s->perm.empty() ? nullptr : s->perm.data());
         // every rotation its own step, last to first; the first rotation undoes nothing
         for (size_t k = count; k-- > 0;)
             launch_pauli_adjoint_step(w.phi, w.lam, n, plan.rots[k], k > 0, s->d_partials, w.d_out + k, s->stream,

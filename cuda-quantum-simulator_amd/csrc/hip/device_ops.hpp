@@ -26,6 +26,32 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
+// The values of a 256-thread work-group added in a fixed order (wave_sum, then the four waves as
+// below); the total is valid in thread 0.  wsum: four doubles of LDS.
+__device__ __forceinline__ double block_sum(double acc, double* wsum) {
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+}
+
+// W(i) = sum_t (-1)^popcount(i & z_t) (cr_t + i ci_t) over the term table `tab` in LDS (the same
+// address in every lane: broadcast reads), added in table order; wi only with IM.  The index type
+// picks the population count: 32 bits where the caller's index has no more.
+__device__ __forceinline__ bool odd_parity(uint32_t v) { return __popc(v) & 1; }
+__device__ __forceinline__ bool odd_parity(uint64_t v) { return __popcll(v) & 1; }
+template <bool IM, class Index>
+__device__ __forceinline__ void term_weight(const ExpectTerm* tab, int nterms, Index i, double& wr, double& wi) {
+    wr = 0.0;
+    wi = 0.0;
+    for (int t = 0; t < nterms; ++t) {
+        const ExpectTerm e = tab[t];
+        const bool neg = odd_parity(i & (Index)e.z);
+        wr += neg ? -e.cr : e.cr;
+        if (IM) wi += neg ? -e.ci : e.ci;
+    }
+}
+
 // Insert a zero bit at each of the `nfix` ascending positions `fix[]` of k.
 __device__ __forceinline__ uint64_t deposit(uint64_t k, int nfix, const int* fix) {
 #pragma unroll

@@ -2124,10 +2124,7 @@ void sample_dist(qsim_dist* d, const double* uniforms, int shots, int64_t* out) 
 
 // QSIM_DIST_EXPECT_OVERLAP (default 1; read at every call): 0 lands every transfer of an
 // expectation value in the one receive buffer and waits for it before its kernels start.
-bool expect_overlap_on() {
-    const char* e = std::getenv("QSIM_DIST_EXPECT_OVERLAP");
-    return e == nullptr || std::atoi(e) != 0;
-}
+bool expect_overlap_on() { return env_switch("QSIM_DIST_EXPECT_OVERLAP", true); }
 
 // <psi|H|psi> of the sharded state (qsim_dist_expectation): see dist_expect.hip.  Everything
 // computes on d->stream; transfer t of the plan lands in the receive buffer (t even) or, while the
@@ -2219,16 +2216,6 @@ double expectation_dist(qsim_dist* d, const qsim_pauli_term* terms, size_t count
 }
 
 // ---- adjoint-method gradients on the sharded state (kernels: dist_adjoint.hip) -------------
-void check_gradient_args(int n, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms, size_t nterms) {
-    if (!gates && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gate list");
-    if (!terms && nterms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
-    for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n);
-    const uint64_t valid = (1ull << n) - 1ull;  // (n <= QSIM_MAX_QUBITS_DIST < 64)
-    for (size_t t = 0; t < nterms; ++t)
-        if ((terms[t].x_mask | terms[t].z_mask) & ~valid)
-            fail(QSIM_ERR_OUT_OF_RANGE, "Pauli term acts on a qubit index out of range");
-}
-
 // The work shards (allocated on first use) and room for nparams x (shards + 1) slots.
 qsim_dist::GradWork& ensure_grad(qsim_dist* d, size_t nparams) {
     if (!d->grad) d->grad = std::make_unique<qsim_dist::GradWork>();

@@ -85,14 +85,6 @@ __device__ __forceinline__ double2 cjmul(double2 a, double2 g) {
     return make_double2(a.x * g.x + a.y * g.y, a.x * g.y - a.y * g.x);
 }
 
-// The 256 threads' values added in a fixed order; the total is returned in thread 0.
-__device__ __forceinline__ double block_sum(double acc, double* wsum) {
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
 // Index k of the active subspace: the whole shard, or (CTRL) the indices with bit cpos set.
 template <bool CTRL>
 __device__ __forceinline__ uint64_t active_index(uint64_t k, int cpos) {

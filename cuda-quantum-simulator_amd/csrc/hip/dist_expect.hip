@@ -21,17 +21,17 @@
 // Either way a rank reads one half of its own shard at k = i with bit b dropped, and the received
 // half at k ^ (x_loc without bit b): two streams of 2^(L-1) amplitudes, contiguous below the
 // lowest set bit of x_loc.
+//
+// This file is the host lowering.  The kernels are expect.hip's k_expect_partial pair under the
+// two-stream addressing policy (launch_dist_expectation, there).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <vector>
 
-#include "device_ops.hpp"
 #include "engine.hpp"
 
 namespace qsim_hip {
-
-// ---- host-only lowering ---------------------------------------------------------------------
 
 DistExpectPlan lower_dist_expectation(int n, int L, const qsim_pauli_term* terms, size_t count, const int* perm) {
     DistExpectPlan p;
@@ -93,121 +93,6 @@ int dist_expect_send_half(const DistExpectTransfer& t, int rank) {
     // what the peer pairs with: its partner's index has bit b flipped (top) or equal
     const int peer_half = dist_expect_own_half(t, (int)((uint64_t)rank ^ t.x_rank));
     return t.top ? 1 - peer_half : peer_half;
-}
-
-// ---- kernels --------------------------------------------------------------------------------
-//
-// k_expect_partial<PAIR>'s scheme on two base pointers: work-group c adds the pairs k = c * 256 +
-// thread, + gridDim.x * 256, ... < count (count = 2^(L-1): a power of two, and xl < count, so
-// k ^ xl < count as well).  ibase: the dropped bit b of the own half, for the sign.
-namespace {
-
-__global__ __launch_bounds__(256) void k_dist_expect_partial(const double2* own, const double2* peer,
-                                                             uint64_t count, uint64_t ibase, uint64_t xl,
-                                                             const ExpectTerm* terms, int nterms,
-                                                             double* partials) {
-    __shared__ ExpectTerm tab[kExpectTerms];
-    __shared__ double wsum[4];
-    for (int t = threadIdx.x; t < nterms; t += 256) tab[t] = terms[t];
-    __syncthreads();
-    double acc = 0.0;
-    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) {
-        const uint64_t i = k | ibase;
-        const double2 a = own[k], b = peer[k ^ xl];
-        const double re = b.x * a.x + b.y * a.y;  // a = conj(psi_J) psi_I
-        const double im = b.x * a.y - b.y * a.x;
-        double wr = 0.0, wi = 0.0;
-        for (int t = 0; t < nterms; ++t) {  // (same LDS address in every lane: broadcast reads)
-            const ExpectTerm e = tab[t];
-            const bool neg = __popcll(i & e.z) & 1;
-            wr += neg ? -e.cr : e.cr;
-            wi += neg ? -e.ci : e.ci;
-        }
-        acc += wr * re + wi * im;
-    }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
-// The z lane/run split of k_expect_partial_split.  No zero is inserted into k here, so the 256
-// consecutive k of a run differ in index bits 0-7 only: thread t evaluates term t's sign over
-// i & ~255 once per run, per amplitude and term there remain a 32-bit AND, one population count
-// and a sign-bit XOR.  The trip count depends on blockIdx only, so every thread reaches both
-// barriers.
-__global__ __launch_bounds__(256) void k_dist_expect_partial_split(const double2* own, const double2* peer,
-                                                                   uint64_t count, uint64_t ibase, uint64_t xl,
-                                                                   const ExpectTerm* terms, int nterms,
-                                                                   double* partials) {
-    __shared__ uint32_t zlo[kExpectTerms];
-    __shared__ double swr[kExpectTerms];
-    __shared__ double swi[kExpectTerms];
-    __shared__ double wsum[4];
-    constexpr uint64_t kLow = 255;
-    ExpectTerm mine{0, 0.0, 0.0};
-    if ((int)threadIdx.x < nterms) {
-        mine = terms[threadIdx.x];
-        zlo[threadIdx.x] = (uint32_t)(mine.z & kLow);
-    }
-    double acc = 0.0;
-    const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t k0 = (uint64_t)blockIdx.x * blockDim.x; k0 < count; k0 += step) {
-        const uint64_t k = k0 + threadIdx.x;
-        const uint64_t i = k | ibase;
-        double re = 0.0, im = 0.0;
-        if (k < count) {
-            const double2 a = own[k], b = peer[k ^ xl];
-            re = b.x * a.x + b.y * a.y;  // a = conj(psi_J) psi_I
-            im = b.x * a.y - b.y * a.x;
-        }
-        __syncthreads();  // the run before has read its weights
-        if ((int)threadIdx.x < nterms) {
-            const bool neg = __popcll(i & ~kLow & mine.z) & 1;  // i & ~255: the same in every thread
-            swr[threadIdx.x] = neg ? -mine.cr : mine.cr;
-            swi[threadIdx.x] = neg ? -mine.ci : mine.ci;
-        }
-        __syncthreads();
-        const uint32_t ilo = (uint32_t)(i & kLow);
-        double wr = 0.0, wi = 0.0;
-#pragma unroll 4
-        for (int t = 0; t < nterms; ++t) {  // (same LDS address in every lane: broadcast reads)
-            const unsigned long long flip = (unsigned long long)(__popc(ilo & zlo[t]) & 1) << 63;
-            wr += __longlong_as_double(__double_as_longlong(swr[t]) ^ flip);
-            wi += __longlong_as_double(__double_as_longlong(swi[t]) ^ flip);
-        }
-        acc += wr * re + wi * im;  // (re = im = 0 past the end)
-    }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
-}  // namespace
-
-void launch_dist_expectation(const double2* own, const double2* peer, int L, int half, uint64_t x_loc,
-                             const ExpectTerm* d_terms, size_t count, double* d_partials, double* d_out,
-                             bool accumulate, hipStream_t s, Timer* tm) {
-    if (count == 0) return;
-    if (L < 1 || (half != 0 && half != 1)) fail(QSIM_ERR_RUNTIME, "bad half-shard of a cross-rank expectation");
-    const uint64_t H = 1ull << (L - 1);
-    const uint64_t xl = x_loc & (H - 1ull);
-    const uint64_t ibase = half ? H : 0ull;
-    const unsigned chunks = (unsigned)std::min<uint64_t>((H + 255) / 256, expect_chunks(1));
-    const bool split_on = expect_split_on();
-    for (size_t t0 = 0; t0 < count; t0 += kExpectTerms) {
-        const int nterms = (int)std::min<size_t>(kExpectTerms, count - t0);
-        const bool split = split_on && nterms >= kExpectSplitMin;
-        {
-            TimedLaunch tl(tm, "dist_expect_cross", 2.0 * 16.0 * (double)H, s);
-            hipLaunchKernelGGL(split ? k_dist_expect_partial_split : k_dist_expect_partial, dim3(chunks), dim3(256),
-                               0, s, own, peer, H, ibase, xl, d_terms + t0, nterms, d_partials);
-            QSIM_HIPCHK(hipGetLastError());
-        }
-        launch_sum_partials(d_partials, (int)chunks, 1, d_out, accumulate || t0 != 0, s);
-    }
 }
 
 }  // namespace qsim_hip

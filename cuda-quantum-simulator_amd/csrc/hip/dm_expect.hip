@@ -103,20 +103,12 @@ __global__ __launch_bounds__(256) void k_dm_expect_partial(const double2* rho, i
         const uint32_t i = i0 + threadIdx.x;
         if (i >= dim) break;  // (n < 8: one run, its upper threads idle)
         const double2 a = rho[(dm_deposit(map, i0, 8, n) | lo) ^ row.xcol];
-        double wr = 0.0, wi = 0.0;
-        for (int t = 0; t < nterms; ++t) {  // (same LDS address in every lane: broadcast reads)
-            const ExpectTerm e = tab[t];
-            const bool neg = __popc(i & (uint32_t)e.z) & 1;
-            wr += neg ? -e.cr : e.cr;
-            wi += neg ? -e.ci : e.ci;
-        }
+        double wr, wi;
+        term_weight<true>(tab, nterms, i, wr, wi);  // (a 32-bit i: the 32-bit population count)
         acc += wr * a.x - wi * a.y;  // Re(W rho)
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        partials[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    acc = block_sum(acc, wsum);
+    if (threadIdx.x == 0) partials[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
 
 }  // namespace

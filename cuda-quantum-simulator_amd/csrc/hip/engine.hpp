@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <cstdlib>
 #include <functional>
 #include <memory>
 #include <stdexcept>
@@ -28,6 +29,12 @@ struct Error : std::runtime_error {
 [[noreturn]] inline void fail(int code, const std::string& m) { throw Error(code, m); }
 // Thread-local message returned by qsim_last_error() (capi.hip).
 void set_last_error(const char* msg);
+// A boolean switch of the environment, read at every call (so a test or a benchmark runs both
+// settings in one process): unset is `dflt`, else whether the value reads as a non-zero integer.
+inline bool env_switch(const char* name, bool dflt) {
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) != 0 : dflt;
+}
 
 #define QSIM_HIPCHK(call)                                                                   \
     do {                                                                                    \
@@ -562,6 +569,9 @@ ExpectPlan lower_pauli_terms(int n, const qsim_pauli_term* terms, size_t count, 
 // positions under perm.
 void check_qubit_perm(int n, const int* perm);
 uint64_t mask_to_physical(uint64_t m, int n, const int* perm);
+// Every x / z mask of the list fits in n (< 64) qubits, else Error (out of range) whose message
+// starts with `what`, the noun for the list's entries ("Pauli term", "Pauli rotation").
+void check_pauli_masks(int n, const qsim_pauli_term* terms, size_t count, const char* what);
 size_t expect_chunks(uint64_t batch);  // partials per trajectory a launch may write
 // d_out[t] = the plan's sum on trajectory t of st ([batch][2^n]); terms: the owner's device copy of
 // the term table (uploaded here), d_partials: batch * expect_chunks(batch) doubles.  Nothing is
@@ -605,8 +615,8 @@ size_t dm_expect_work_doubles(const DmExpectPlan& plan);  // doubles of d_work a
 void launch_dm_expectation(const double2* rho, const DmExpectPlan& plan, DevBuf& table, double* d_work,
                            double* d_out, hipStream_t s, Timer* tm);
 
-// Pauli-sum expectation values on a sharded state (dist_expect.hip; the transfers and collectives
-// around it: dist.hip).  A physical x mask splits into local bits (< L) and rank bits:
+// Pauli-sum expectation values on a sharded state (lowering: dist_expect.hip; the launch: expect.hip;
+// the transfers and collectives around it: dist.hip).  A physical x mask splits into local bits (< L) and rank bits:
 // x = x_loc | x_rank << L.  Groups with x_rank == 0 pair inside a shard (launch_expectation on the
 // shard, n = L); a group with x_rank != 0 pairs shard r with shard r ^ x_rank and needs half of
 // the peer's shard.  Cross groups with the same key (x_rank, top local position in x_loc) share
@@ -655,6 +665,9 @@ bool gate_is_parameterised(int type);
 qsim_gate gate_inverse(const qsim_gate& g);    // S <-> Sdag, T <-> Tdag, rotations: angle negated
 Generator gate_generator(const qsim_gate& g);  // of a parameterised gate, on the gate's own qubits
 bool adjoint_fused_on();                       // QSIM_ADJOINT_FUSED (default 1), read at every call
+// The arguments of a gradient call or plan (single state and sharded): null lists (invalid
+// argument), every gate against n qubits (validate_gate), the observable's masks (out of range).
+void check_gradient_args(int n, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms, size_t nterms);
 // The terms of dst = H src, merged and grouped by physical x mask like lower_expectation; a term's
 // (cr, ci) is its complex weight c (-i)^nY (the kernel adds the sign (-1)^popcount(i & z)).
 ExpectPlan lower_pauli_apply(int n, const qsim_pauli_term* terms, size_t count, const int* perm);

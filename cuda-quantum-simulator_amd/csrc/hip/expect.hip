@@ -20,7 +20,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdlib>
 #include <functional>
 #include <map>
 #include <utility>
@@ -50,19 +49,23 @@ uint64_t mask_to_physical(uint64_t m, int n, const int* perm) {
     return p;
 }
 
+void check_pauli_masks(int n, const qsim_pauli_term* terms, size_t count, const char* what) {
+    const uint64_t valid = (1ull << n) - 1ull;
+    for (size_t t = 0; t < count; ++t)
+        if ((terms[t].x_mask | terms[t].z_mask) & ~valid)
+            fail(QSIM_ERR_OUT_OF_RANGE, std::string(what) + " acts on a qubit index out of range");
+}
+
 ExpectPlan lower_pauli_terms(int n, const qsim_pauli_term* terms, size_t count, const int* perm,
                              const std::function<void(uint64_t, uint64_t, double, ExpectTerm&)>& weight) {
     check_qubit_perm(n, perm);
     if (count && !terms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
-    const uint64_t valid = (1ull << n) - 1ull;
+    check_pauli_masks(n, terms, count, "Pauli term");
     auto to_phys = [&](uint64_t m) { return mask_to_physical(m, n, perm); };
     // merged coefficients keyed by the physical (x, z): iteration order is by x, then z
     std::map<std::pair<uint64_t, uint64_t>, double> merged;
-    for (size_t t = 0; t < count; ++t) {
-        if ((terms[t].x_mask | terms[t].z_mask) & ~valid)
-            fail(QSIM_ERR_OUT_OF_RANGE, "Pauli term acts on a qubit index out of range");
+    for (size_t t = 0; t < count; ++t)
         merged[{to_phys(terms[t].x_mask), to_phys(terms[t].z_mask)}] += terms[t].coeff;
-    }
     ExpectPlan plan;
     for (const auto& kv : merged) {
         const uint64_t x = kv.first.first, z = kv.first.second;
@@ -102,99 +105,119 @@ size_t expect_chunks(uint64_t batch) {
 
 namespace {
 
+// Addressing policies of the two kernels below: how pair number k of a launch turns into the sign
+// index i (sign_index) and into Re a / Im a (product; off: the trajectory's offset).  kLow: the
+// index bits in which the 256 consecutive k of a work-group's run differ.
+
+// re + i im = conj(b) a
+__device__ __forceinline__ void conj_product(double2 a, double2 b, double& re, double& im) {
+    re = b.x * a.x + b.y * a.y;
+    im = b.x * a.y - b.y * a.x;
+}
+
+// x == 0: amplitude i = k on its own, Re a = |psi_i|^2.
+struct DiagAddr {
+    static constexpr bool kPair = false;
+    static constexpr uint64_t kLow = 511;
+    const double2* st;
+    __device__ uint64_t sign_index(uint64_t k) const { return k; }
+    __device__ void product(uint64_t off, uint64_t, uint64_t i, double& re, double& im) const {
+        const double2 a = st[off + i];
+        re = a.x * a.x + a.y * a.y;
+        im = 0.0;
+    }
+};
+
+// x != 0 inside one state: i = insert0(k, hbit) (hbit: the highest x bit) with i ^ x,
+// a = conj(psi_j) psi_i.  (kLow has bit 8: the inserted zero may fall below it.)
+struct PairAddr {
+    static constexpr bool kPair = true;
+    static constexpr uint64_t kLow = 511;
+    const double2* st;
+    int hbit;
+    uint64_t x;
+    __device__ uint64_t sign_index(uint64_t k) const {
+        const uint64_t lo = k & ((1ull << hbit) - 1ull);
+        return ((k ^ lo) << 1) | lo;
+    }
+    __device__ void product(uint64_t off, uint64_t, uint64_t i, double& re, double& im) const {
+        const double2* v = st + off;
+        conj_product(v[i], v[i ^ x], re, im);
+    }
+};
+
+// A cross-rank group of a sharded state (dist_expect.hip) on two base pointers: own[k] with
+// peer[k ^ xl], a = conj(psi_J) psi_I (count = 2^(L-1): a power of two, and xl < count, so
+// k ^ xl < count as well).  ibase: the dropped bit b of the own half, for the sign.  No zero is
+// inserted into k, so the k of a run differ in index bits 0-7 only.  (One state: gridDim.y == 1.)
+struct TwoStreamAddr {
+    static constexpr bool kPair = true;
+    static constexpr uint64_t kLow = 255;
+    const double2 *own, *peer;
+    uint64_t ibase, xl;
+    __device__ uint64_t sign_index(uint64_t k) const { return k | ibase; }
+    __device__ void product(uint64_t, uint64_t k, uint64_t, double& re, double& im) const {
+        conj_product(own[k], peer[k ^ xl], re, im);
+    }
+};
+
 // One launch of one group over `gridDim.y` trajectories: work-group (c, t) adds the pairs
-// k = c * 256 + thread, + gridDim.x * 256, ... < count of trajectory t.  PAIR: x != 0, pair k is
-// i = insert0(k, hbit) with i ^ x (hbit: the highest x bit); else i = k on its own.
-template <bool PAIR>
-__global__ __launch_bounds__(256) void k_expect_partial(const double2* st, uint64_t stride, uint64_t count,
-                                                        int hbit, uint64_t x, const ExpectTerm* terms, int nterms,
-                                                        double* partials) {
+// k = c * 256 + thread, + gridDim.x * 256, ... < count of trajectory t.
+template <class Addr>
+__global__ __launch_bounds__(256) void k_expect_partial(Addr addr, uint64_t stride, uint64_t count,
+                                                        const ExpectTerm* terms, int nterms, double* partials) {
     __shared__ ExpectTerm tab[kExpectTerms];
     __shared__ double wsum[4];
     for (int t = threadIdx.x; t < nterms; t += 256) tab[t] = terms[t];
     __syncthreads();
-    const double2* v = st + (uint64_t)blockIdx.y * stride;
-    const uint64_t lomask = PAIR ? (1ull << hbit) - 1ull : 0ull;
+    const uint64_t off = (uint64_t)blockIdx.y * stride;
     double acc = 0.0;
     const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; k < count; k += step) {
-        uint64_t i = k;
-        double re, im = 0.0;
-        if (PAIR) {
-            const uint64_t lo = k & lomask;
-            i = ((k ^ lo) << 1) | lo;
-            const double2 a = v[i], b = v[i ^ x];
-            re = b.x * a.x + b.y * a.y;  // a = conj(psi_j) psi_i
-            im = b.x * a.y - b.y * a.x;
-        } else {
-            const double2 a = v[i];
-            re = a.x * a.x + a.y * a.y;
-        }
-        double wr = 0.0, wi = 0.0;
-        for (int t = 0; t < nterms; ++t) {  // (same LDS address in every lane: broadcast reads)
-            const ExpectTerm e = tab[t];
-            const bool neg = __popcll(i & e.z) & 1;
-            wr += neg ? -e.cr : e.cr;
-            if (PAIR) wi += neg ? -e.ci : e.ci;
-        }
-        acc += PAIR ? wr * re + wi * im : wr * re;
+        const uint64_t i = addr.sign_index(k);
+        double re, im, wr, wi;
+        addr.product(off, k, i, re, im);
+        term_weight<Addr::kPair>(tab, nterms, i, wr, wi);
+        acc += Addr::kPair ? wr * re + wi * im : wr * re;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        partials[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    acc = block_sum(acc, wsum);
+    if (threadIdx.x == 0) partials[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
 }
 
 // The same launch with each z split in two (groups of many terms are instruction-bound on the
 // per-amplitude, per-term sign: a 64-bit AND, two population counts and a select).  A work-group's
-// 256 consecutive pairs differ only in index bits 0-8 (bit 8: the inserted zero may fall below
-// it), so (-1)^popcount(i & z) = (-1)^popcount(i & z & ~511) (-1)^popcount(i & z & 511): thread t
-// evaluates the first factor of term t once per 256-pair run and stores the signed weights in
-// LDS; per amplitude and term there remain a 32-bit AND, one population count and a sign-bit XOR.
-// The trip count depends on blockIdx only, so every thread reaches both barriers.
-template <bool PAIR>
-__global__ __launch_bounds__(256) void k_expect_partial_split(const double2* st, uint64_t stride, uint64_t count,
-                                                              int hbit, uint64_t x, const ExpectTerm* terms,
-                                                              int nterms, double* partials) {
+// 256 consecutive pairs differ only in the index bits of kLow, so (-1)^popcount(i & z) =
+// (-1)^popcount(i & z & ~kLow) (-1)^popcount(i & z & kLow): thread t evaluates the first factor of
+// term t once per 256-pair run and stores the signed weights in LDS; per amplitude and term there
+// remain a 32-bit AND, one population count and a sign-bit XOR.  The trip count depends on
+// blockIdx only, so every thread reaches both barriers.
+template <class Addr>
+__global__ __launch_bounds__(256) void k_expect_partial_split(Addr addr, uint64_t stride, uint64_t count,
+                                                              const ExpectTerm* terms, int nterms,
+                                                              double* partials) {
     __shared__ uint32_t zlo[kExpectTerms];
     __shared__ double swr[kExpectTerms];
-    __shared__ double swi[PAIR ? kExpectTerms : 1];
+    __shared__ double swi[Addr::kPair ? kExpectTerms : 1];
     __shared__ double wsum[4];
-    constexpr uint64_t kLow = 511;
+    constexpr uint64_t kLow = Addr::kLow;
     ExpectTerm mine{0, 0.0, 0.0};
     if ((int)threadIdx.x < nterms) {
         mine = terms[threadIdx.x];
         zlo[threadIdx.x] = (uint32_t)(mine.z & kLow);
     }
-    const double2* v = st + (uint64_t)blockIdx.y * stride;
-    const uint64_t lomask = PAIR ? (1ull << hbit) - 1ull : 0ull;
+    const uint64_t off = (uint64_t)blockIdx.y * stride;
     double acc = 0.0;
     const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t k0 = (uint64_t)blockIdx.x * blockDim.x; k0 < count; k0 += step) {
         const uint64_t k = k0 + threadIdx.x;
-        const bool active = k < count;
-        uint64_t i = k;
-        if (PAIR) {
-            const uint64_t lo = k & lomask;
-            i = ((k ^ lo) << 1) | lo;
-        }
+        const uint64_t i = addr.sign_index(k);
         double re = 0.0, im = 0.0;
-        if (active) {
-            if (PAIR) {
-                const double2 a = v[i], b = v[i ^ x];
-                re = b.x * a.x + b.y * a.y;  // a = conj(psi_j) psi_i
-                im = b.x * a.y - b.y * a.x;
-            } else {
-                const double2 a = v[i];
-                re = a.x * a.x + a.y * a.y;
-            }
-        }
+        if (k < count) addr.product(off, k, i, re, im);
         __syncthreads();  // the run before has read its weights
         if ((int)threadIdx.x < nterms) {
-            const bool neg = __popcll(i & ~kLow & mine.z) & 1;  // i & ~511: the same in every thread
+            const bool neg = __popcll(i & ~kLow & mine.z) & 1;  // i & ~kLow: the same in every thread
             swr[threadIdx.x] = neg ? -mine.cr : mine.cr;
-            if (PAIR) swi[threadIdx.x] = neg ? -mine.ci : mine.ci;
+            if (Addr::kPair) swi[threadIdx.x] = neg ? -mine.ci : mine.ci;
         }
         __syncthreads();
         const uint32_t ilo = (uint32_t)(i & kLow);
@@ -203,25 +226,30 @@ __global__ __launch_bounds__(256) void k_expect_partial_split(const double2* st,
         for (int t = 0; t < nterms; ++t) {  // (same LDS address in every lane: broadcast reads)
             const unsigned long long flip = (unsigned long long)(__popc(ilo & zlo[t]) & 1) << 63;
             wr += __longlong_as_double(__double_as_longlong(swr[t]) ^ flip);
-            if (PAIR) wi += __longlong_as_double(__double_as_longlong(swi[t]) ^ flip);
+            if (Addr::kPair) wi += __longlong_as_double(__double_as_longlong(swi[t]) ^ flip);
         }
-        acc += PAIR ? wr * re + wi * im : wr * re;  // (re = im = 0 past the end)
+        acc += Addr::kPair ? wr * re + wi * im : wr * re;  // (re = im = 0 past the end)
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        partials[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    acc = block_sum(acc, wsum);
+    if (threadIdx.x == 0) partials[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = acc;
+}
+
+// One launch of at most kExpectTerms terms of one group: the split kernel from kExpectSplitMin
+// terms on, unless QSIM_EXPECT_SPLIT says otherwise.
+template <class Addr>
+void launch_partial(const Addr& addr, dim3 grid, uint64_t stride, uint64_t count, const ExpectTerm* d_terms,
+                    int nterms, bool split_on, double* d_partials, hipStream_t s) {
+    const bool split = split_on && nterms >= kExpectSplitMin;
+    hipLaunchKernelGGL(split ? k_expect_partial_split<Addr> : k_expect_partial<Addr>, grid, dim3(256), 0, s, addr,
+                       stride, count, d_terms, nterms, d_partials);
+    QSIM_HIPCHK(hipGetLastError());
 }
 
 }  // namespace
 
 // QSIM_EXPECT_SPLIT (default 1; read at every call, so a benchmark can time both kernels in one
 // process): 0 runs every group through the plain kernel.
-bool expect_split_on() {
-    const char* e = std::getenv("QSIM_EXPECT_SPLIT");
-    return e == nullptr || std::atoi(e) != 0;
-}
+bool expect_split_on() { return env_switch("QSIM_EXPECT_SPLIT", true); }
 
 void launch_expectation(const double2* st, int n, uint64_t batch, const ExpectPlan& plan, DevBuf& terms,
                         double* d_partials, double* d_out, hipStream_t s, Timer* tm) {
@@ -240,21 +268,42 @@ void launch_expectation(const double2* st, int n, uint64_t batch, const ExpectPl
         const unsigned chunks = (unsigned)std::min<uint64_t>((count + 255) / 256, max_chunks);
         for (size_t t0 = g.begin; t0 < g.end; t0 += kExpectTerms) {
             const int nterms = (int)std::min<size_t>(kExpectTerms, g.end - t0);
-            const bool split = split_on && nterms >= kExpectSplitMin;
-            auto kernel = pair ? (split ? k_expect_partial_split<true> : k_expect_partial<true>)
-                               : (split ? k_expect_partial_split<false> : k_expect_partial<false>);
             for (uint64_t b0 = 0; b0 < batch; b0 += kMaxGridY) {
                 const unsigned nb = (unsigned)std::min<uint64_t>(kMaxGridY, batch - b0);
+                const double2* v = st + b0 * N;
                 {
                     TimedLaunch tl(tm, pair ? "expect_pair" : "expect_diag", 16.0 * (double)N * nb, s);
-                    hipLaunchKernelGGL(kernel, dim3(chunks, nb), dim3(256), 0, s, st + b0 * N, N, count, hbit, g.x,
-                                       d_terms + t0, nterms, d_partials);
-                    QSIM_HIPCHK(hipGetLastError());
+                    if (pair)
+                        launch_partial(PairAddr{v, hbit, g.x}, dim3(chunks, nb), N, count, d_terms + t0, nterms,
+                                       split_on, d_partials, s);
+                    else
+                        launch_partial(DiagAddr{v}, dim3(chunks, nb), N, count, d_terms + t0, nterms, split_on,
+                                       d_partials, s);
                 }
                 launch_sum_partials(d_partials, (int)chunks, nb, d_out + b0, !first, s);
             }
             first = false;
         }
+    }
+}
+
+// A cross-rank group of a sharded state (dist_expect.hip): the same kernels on two streams.
+void launch_dist_expectation(const double2* own, const double2* peer, int L, int half, uint64_t x_loc,
+                             const ExpectTerm* d_terms, size_t count, double* d_partials, double* d_out,
+                             bool accumulate, hipStream_t s, Timer* tm) {
+    if (count == 0) return;
+    if (L < 1 || (half != 0 && half != 1)) fail(QSIM_ERR_RUNTIME, "bad half-shard of a cross-rank expectation");
+    const uint64_t H = 1ull << (L - 1);
+    const TwoStreamAddr addr{own, peer, half ? H : 0ull, x_loc & (H - 1ull)};
+    const unsigned chunks = (unsigned)std::min<uint64_t>((H + 255) / 256, expect_chunks(1));
+    const bool split_on = expect_split_on();
+    for (size_t t0 = 0; t0 < count; t0 += kExpectTerms) {
+        const int nterms = (int)std::min<size_t>(kExpectTerms, count - t0);
+        {
+            TimedLaunch tl(tm, "dist_expect_cross", 2.0 * 16.0 * (double)H, s);
+            launch_partial(addr, dim3(chunks), 0, H, d_terms + t0, nterms, split_on, d_partials, s);
+        }
+        launch_sum_partials(d_partials, (int)chunks, 1, d_out, accumulate || t0 != 0, s);
     }
 }
 

@@ -40,10 +40,7 @@ namespace qsim_hip {
 PauliRotPlan lower_pauli_rotations(int n, const qsim_pauli_term* rots, size_t count, const int* perm) {
     check_qubit_perm(n, perm);
     if (count && !rots) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
-    const uint64_t valid = (1ull << n) - 1ull;
-    for (size_t t = 0; t < count; ++t)  // (the whole sequence: a caller lowers before it launches)
-        if ((rots[t].x_mask | rots[t].z_mask) & ~valid)
-            fail(QSIM_ERR_OUT_OF_RANGE, "Pauli rotation acts on a qubit index out of range");
+    check_pauli_masks(n, rots, count, "Pauli rotation");  // (the whole sequence: a caller lowers before it launches)
     auto to_phys = [&](uint64_t m) { return mask_to_physical(m, n, perm); };
     PauliRotPlan plan;
     plan.rots.reserve(count);
@@ -81,14 +78,6 @@ uint64_t pauli_stream_blocks() {
 }
 
 namespace {
-
-// The 256 threads' values added in a fixed order; every thread returns the total.
-__device__ __forceinline__ double block_sum(double acc, double* wsum) {
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    return (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
 
 // Pair k: a zero inserted at position hbit (lomask = 2^hbit - 1).
 __device__ __forceinline__ uint64_t insert0(uint64_t k, uint64_t lomask) {

@@ -68,10 +68,8 @@ __global__ __launch_bounds__(256) void k_norm_partial(const double2* st, uint64_
         const double2 a = st[i];
         acc += a.x * a.x + a.y * a.y;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) partials[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    acc = block_sum(acc, wsum);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
 
 // result[r] (+)= the `count` partials of row r (work-group r), added in a fixed order.
@@ -81,13 +79,8 @@ __global__ __launch_bounds__(256) void k_sum_partials(const double* partials, in
     const double* p = partials + (uint64_t)blockIdx.x * count;
     double acc = 0.0;
     for (int i = threadIdx.x; i < count; i += 256) acc += p[i];
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const double sum = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-        result[blockIdx.x] = accumulate ? result[blockIdx.x] + sum : sum;
-    }
+    const double sum = block_sum(acc, wsum);
+    if (threadIdx.x == 0) result[blockIdx.x] = accumulate ? result[blockIdx.x] + sum : sum;
 }
 
 void launch_sum_partials(const double* partials, int count, unsigned rows, double* result, bool accumulate,
@@ -200,10 +193,8 @@ __global__ __launch_bounds__(256) void k_chunk_sums(const double2* st, uint64_t 
         const double2 a = st[base + i];
         acc += a.x * a.x + a.y * a.y;
     }
-    acc = wave_sum(acc);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) sums[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    acc = block_sum(acc, wsum);
+    if (threadIdx.x == 0) sums[blockIdx.x] = acc;
 }
 
 // shot s: search chunk `chunk_of[s]` (global over the batch) for the first i with prefix >=

@@ -1280,6 +1280,8 @@ struct qsim_dist {
     Scratch readout;  // sampling / probabilities / broadcast temporaries (dist readout entries)
     // per shard: the signed term tables of the last expectation value (dist_expect.hip)
     std::vector<std::unique_ptr<DevBuf>> expect_local, expect_cross;
+    // per shard: the signed angle tables of the last rotation sequence's phase runs (dist_pauli_rot.hip)
+    std::vector<std::unique_ptr<DevBuf>> rot_terms;
     // Adjoint-method gradients (gradient_dist): the two work shards per shard of this process, the
     // per-shard term tables of H, the (parameter, shard) slots, and the plans of the inverted
     // segments, keyed like run plans by (gate list, map at the start).  Absent until the first
@@ -2122,6 +2124,15 @@ void sample_dist(qsim_dist* d, const double* uniforms, int shots, int64_t* out) 
     for (int s = 0; s < shots; ++s) out[s] = chunk_of[s] < 0 ? (int64_t)(1ull << n) : (int64_t)idx[s];
 }
 
+// At least `count` events in d->events (the remap pipeline's; the readers below use the first few
+// between remaps).
+void ensure_events(qsim_dist* d, size_t count) {
+    const size_t have = d->events.size();
+    if (have >= count) return;
+    d->events.resize(count, nullptr);
+    for (size_t i = have; i < count; ++i) QSIM_HIPCHK(hipEventCreateWithFlags(&d->events[i], hipEventDisableTiming));
+}
+
 // QSIM_DIST_EXPECT_OVERLAP (default 1; read at every call): 0 lands every transfer of an
 // expectation value in the one receive buffer and waits for it before its kernels start.
 bool expect_overlap_on() { return env_switch("QSIM_DIST_EXPECT_OVERLAP", true); }
@@ -2148,12 +2159,7 @@ double expectation_dist(qsim_dist* d, const qsim_pauli_term* terms, size_t count
     QSIM_HIPCHK(hipMemsetAsync(d_slots, 0, nslots * sizeof(double), d->stream));
     const bool overlap = expect_overlap_on();
     const double sent_before = d->sent_bytes;  // (remapBytes() stays the last run's)
-    if (!plan.transfers.empty() && d->events.size() < 5) {
-        const size_t have = d->events.size();
-        d->events.resize(5, nullptr);
-        for (size_t i = have; i < d->events.size(); ++i)
-            QSIM_HIPCHK(hipEventCreateWithFlags(&d->events[i], hipEventDisableTiming));
-    }
+    if (!plan.transfers.empty()) ensure_events(d, 5);
     auto buffer_of = [&](size_t t) { return overlap ? (int)(t & 1) : 0; };
     auto post = [&](size_t t) {  // transfer t on comm_stream, into buffer_of(t)
         const DistExpectTransfer& tr = plan.transfers[t];
@@ -2251,6 +2257,54 @@ qsim_dist::GradWork& ensure_grad(qsim_dist* d, size_t nparams) {
     }
     while (w.terms.size() < S) w.terms.emplace_back(new DevBuf());
     return w;
+}
+
+// The sweep's two work states from the state where it lies: phi = the state, lambda = H phi under
+// the same map (events 0 and 1 of d->events: free outside remaps).
+void grad_load_work(qsim_dist* d, qsim_dist::GradWork& w, const DistApplyPlan& ap) {
+    const int L = d->L;
+    const size_t S = d->shards.size();
+    if (ap.cross_groups && d->world == 1) fail(QSIM_ERR_RUNTIME, "cross-rank Pauli group in a world of one");
+    ensure_events(d, 5);
+    const uint64_t amps = 1ull << L;
+    for (size_t i = 0; i < S; ++i) {
+        QSIM_HIPCHK(hipMemcpyAsync(w.phi[i], d->shards[i].d, amps * sizeof(double2), hipMemcpyDeviceToDevice, d->stream));
+        const std::vector<ExpectTerm> tab = dist_apply_terms(ap, L, d->shards[i].rank);
+        w.terms[i]->upload(tab.data(), tab.size() * sizeof(ExpectTerm), d->stream);
+    }
+    std::vector<char> first(S, 1);
+    uint64_t landed = 0;  // x_rank of the phi shards in the receive buffers
+    for (const DistApplyGroup& g : ap.groups) {
+        if (g.x_rank != 0 && g.x_rank != landed) {
+            QSIM_HIPCHK(hipEventRecord(d->events[0], d->stream));  // phi written, the buffer's readers done
+            QSIM_HIPCHK(hipStreamWaitEvent(d->comm_stream, d->events[0], 0));
+            std::vector<Post> posts;
+            for (size_t i = 0; i < S; ++i) {
+                const Shard& sh = d->shards[i];
+                posts.push_back({sh.rank, (int)((uint64_t)sh.rank ^ g.x_rank), w.phi[i], sh.recvbuf, amps});
+            }
+            post_transfers(d, posts, "gradient H phi shard send/recv");
+            QSIM_HIPCHK(hipEventRecord(d->events[1], d->comm_stream));
+            QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[1], 0));
+            landed = g.x_rank;
+        }
+        for (size_t i = 0; i < S; ++i) {
+            const double2* src = g.x_rank ? d->shards[i].recvbuf : w.phi[i];
+            launch_pauli_apply_group(src, w.lam[i], L, g.x_loc, (const ExpectTerm*)w.terms[i]->ptr + g.begin,
+                                     g.end - g.begin, first[i] != 0, d->stream, &d->timer);
+            first[i] = 0;
+        }
+    }
+}
+
+// grad[j] for j < P from the slots [parameter j][shard i]: the shards of this process in rank
+// order, then the ranks: one vector all-reduce.
+void grad_reduce(qsim_dist* d, qsim_dist::GradWork& w, size_t P, double* out) {
+    const size_t S = d->shards.size();
+    double* d_tot = w.d_slots + P * S;
+    launch_sum_partials(w.d_slots, (int)S, (unsigned)P, d_tot, false, d->stream);
+    allreduce_vec(d, d_tot, P, out);
+    stream_wait(d, d->comm_stream);
 }
 
 // One inverted run of non-parameterised gates (execution order, logical qubits) on both work
@@ -2415,45 +2469,9 @@ void gradient_dist(qsim_dist* d, const qsim_gate* gates, size_t count, const qsi
     *value = expectation_dist(d, terms, nterms);
     if (!wp) return;
     qsim_dist::GradWork& w = *wp;
-    if (ap.cross_groups && d->world == 1) fail(QSIM_ERR_RUNTIME, "cross-rank Pauli group in a world of one");
-    if (d->events.size() < 5) {
-        const size_t have = d->events.size();
-        d->events.resize(5, nullptr);
-        for (size_t i = have; i < d->events.size(); ++i)
-            QSIM_HIPCHK(hipEventCreateWithFlags(&d->events[i], hipEventDisableTiming));
-    }
     const double sent_before = d->sent_bytes;  // (remapBytes() stays the forward run's)
     std::vector<int> wperm = d->perm;
-    const uint64_t amps = 1ull << L;
-    // phi: the state where it lies; lambda = H phi under the same map
-    for (size_t i = 0; i < S; ++i) {
-        QSIM_HIPCHK(hipMemcpyAsync(w.phi[i], d->shards[i].d, amps * sizeof(double2), hipMemcpyDeviceToDevice, d->stream));
-        const std::vector<ExpectTerm> tab = dist_apply_terms(ap, L, d->shards[i].rank);
-        w.terms[i]->upload(tab.data(), tab.size() * sizeof(ExpectTerm), d->stream);
-    }
-    std::vector<char> first(S, 1);
-    uint64_t landed = 0;  // x_rank of the phi shards in the receive buffers
-    for (const DistApplyGroup& g : ap.groups) {
-        if (g.x_rank != 0 && g.x_rank != landed) {
-            QSIM_HIPCHK(hipEventRecord(d->events[0], d->stream));  // phi written, the buffer's readers done
-            QSIM_HIPCHK(hipStreamWaitEvent(d->comm_stream, d->events[0], 0));
-            std::vector<Post> posts;
-            for (size_t i = 0; i < S; ++i) {
-                const Shard& sh = d->shards[i];
-                posts.push_back({sh.rank, (int)((uint64_t)sh.rank ^ g.x_rank), w.phi[i], sh.recvbuf, amps});
-            }
-            post_transfers(d, posts, "gradient H phi shard send/recv");
-            QSIM_HIPCHK(hipEventRecord(d->events[1], d->comm_stream));
-            QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[1], 0));
-            landed = g.x_rank;
-        }
-        for (size_t i = 0; i < S; ++i) {
-            const double2* src = g.x_rank ? d->shards[i].recvbuf : w.phi[i];
-            launch_pauli_apply_group(src, w.lam[i], L, g.x_loc, (const ExpectTerm*)w.terms[i]->ptr + g.begin,
-                                     g.end - g.begin, first[i] != 0, d->stream, &d->timer);
-            first[i] = 0;
-        }
-    }
+    grad_load_work(d, w, ap);
     // the sweep: slot [parameter j][shard i]
     const size_t P = params.size();
     QSIM_HIPCHK(hipMemsetAsync(w.d_slots, 0, P * (S + 1) * sizeof(double), d->stream));
@@ -2472,12 +2490,8 @@ void gradient_dist(qsim_dist* d, const qsim_gate* gates, size_t count, const qsi
         --j;
         grad_step(d, w, inv_gate, wperm, w.d_slots + j * S, k == first_param, fused_step);
     }
-    // the shards of this process in rank order, then the ranks: one vector all-reduce
-    double* d_tot = w.d_slots + P * S;
-    launch_sum_partials(w.d_slots, (int)S, (unsigned)P, d_tot, false, d->stream);
     std::vector<double> tot(P, 0.0);
-    allreduce_vec(d, d_tot, P, tot.data());
-    stream_wait(d, d->comm_stream);
+    grad_reduce(d, w, P, tot.data());
     for (size_t q = 0; q < P; ++q) grad[params[q]] = tot[q];
     d->sent_bytes = sent_before;
 }
@@ -2538,6 +2552,164 @@ void gradient_plan_host(int n, int g, std::vector<int> perm, const qsim_gate* ga
     for (int q = 0; q < n; ++q) out->perm_after_sweep[q] = perm[q];
     out->bytes_sent_per_rank =
         (uint64_t)(out->apply_transfers + out->step_transfers) * ((uint64_t)sizeof(double2) << L);
+}
+
+// ---- Pauli-string rotations on the sharded state (kernels: dist_pauli_rot.hip, pauli_rot.hip) ----
+// The peers' whole shards `src` (one per shard of this process, this rank's own data) into the
+// staging buffers (recv: the receive buffers, else the send buffers) for the pairing r <-> r ^ x_rank,
+// on the comm stream after everything queued on d->stream so far (event 0: src written, the
+// buffer's last readers done); `landed` is recorded when the shards have arrived.
+void post_peer_shards(qsim_dist* d, const std::vector<double2*>& src, uint64_t x_rank, bool recv, hipEvent_t landed,
+                      const char* what) {
+    QSIM_HIPCHK(hipEventRecord(d->events[0], d->stream));
+    QSIM_HIPCHK(hipStreamWaitEvent(d->comm_stream, d->events[0], 0));
+    std::vector<Post> posts;
+    for (size_t i = 0; i < d->shards.size(); ++i) {
+        const Shard& sh = d->shards[i];
+        posts.push_back({sh.rank, (int)((uint64_t)sh.rank ^ x_rank), src[i], recv ? sh.recvbuf : sh.sendbuf,
+                         1ull << d->L});
+    }
+    post_transfers(d, posts, what);
+    QSIM_HIPCHK(hipEventRecord(landed, d->comm_stream));
+}
+
+// The sequence on the state's shards, in order (qsim_dist_apply_pauli_rotations).  A cross rotation
+// sends each shard itself; its kernel, the shard's next writer, waits for the transfer (event 1),
+// which has then read the shard on this rank and landed the peer's in the receive buffer.
+void pauli_rotations_dist(qsim_dist* d, const DistPauliRotPlan& plan) {
+    const int L = d->L;
+    const size_t S = d->shards.size();
+    if (plan.cross && d->world == 1) fail(QSIM_ERR_RUNTIME, "cross-rank Pauli rotation in a world of one");
+    if (plan.cross) ensure_events(d, 5);
+    const double sent_before = d->sent_bytes;  // (remapBytes() stays the last run's)
+    // every phase run's table in one upload per shard (sequence order), before the first launch
+    if (plan.phase) {
+        while (d->rot_terms.size() < S) d->rot_terms.emplace_back(new DevBuf());
+        for (size_t i = 0; i < S; ++i) {
+            std::vector<ExpectTerm> tab;
+            tab.reserve(plan.phase);
+            for (const DistPauliRot& r : plan.rots)
+                if (r.cls == DPR_PHASE) tab.push_back(ExpectTerm{r.z_loc, dist_pauli_shard_rot(r, d->shards[i].rank).theta, 0.0});
+            d->rot_terms[i]->upload(tab.data(), tab.size() * sizeof(ExpectTerm), d->stream);
+        }
+    }
+    std::vector<double2*> own(S);
+    for (size_t i = 0; i < S; ++i) own[i] = d->shards[i].d;
+    size_t done = 0;  // phase rotations launched so far
+    for (size_t k = 0; k < plan.rots.size();) {
+        const DistPauliRot& r = plan.rots[k];
+        if (r.cls == DPR_PHASE) {
+            size_t end = k;
+            while (end < plan.rots.size() && plan.rots[end].cls == DPR_PHASE) ++end;
+            for (size_t i = 0; i < S; ++i)
+                launch_pauli_phase(own[i], L, (const ExpectTerm*)d->rot_terms[i]->ptr + done, end - k, d->stream, &d->timer);
+            done += end - k;
+            k = end;
+            continue;
+        }
+        if (r.cls == DPR_LOCAL) {
+            for (size_t i = 0; i < S; ++i)
+                launch_pauli_rot(own[i], L, dist_pauli_shard_rot(r, d->shards[i].rank), d->stream, &d->timer);
+        } else {
+            post_peer_shards(d, own, r.x_rank, true, d->events[1], "Pauli rotation shard send/recv");
+            QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[1], 0));
+            for (size_t i = 0; i < S; ++i)
+                launch_dist_pauli_rot(own[i], d->shards[i].recvbuf, nullptr, L, r, d->shards[i].rank, false, true,
+                                      d->d_partials, nullptr, d->stream, &d->timer);
+        }
+        ++k;
+    }
+    d->sent_bytes = sent_before;
+}
+
+// One step of the rotation sweep (pauli_gradient_dist): slots[i] = shard i's share of
+// Im <lambda| P |phi>, then exp(+i theta/2 P) on both work states; last (the sequence's first
+// rotation): the bra-ket alone.  A cross step receives the peer's old phi shard (receive buffer,
+// event 1), then its old lambda shard (send buffer, event 2): both transfers are queued before
+// the first kernel, so lambda crosses while phi is updated, and each work shard is overwritten
+// only after the transfer that sends it has completed.
+void pauli_grad_step(qsim_dist* d, qsim_dist::GradWork& w, const DistPauliRot& r, double* slots, bool last) {
+    const int L = d->L;
+    const size_t S = d->shards.size();
+    if (r.cls != DPR_CROSS) {
+        for (size_t i = 0; i < S; ++i) {
+            const int rank = d->shards[i].rank;
+            launch_pauli_adjoint_step(w.phi[i], w.lam[i], L, PauliRot{r.x_loc, r.z_loc, r.theta}, !last, d->d_partials,
+                                      slots + i, d->stream, &d->timer, dist_pauli_rank_neg(r, rank));
+        }
+        return;
+    }
+    if (d->world == 1) fail(QSIM_ERR_RUNTIME, "cross-rank gradient step in a world of one");
+    post_peer_shards(d, w.phi, r.x_rank, true, d->events[1], "Pauli gradient phi shard send/recv");
+    if (!last) {
+        std::vector<Post> posts;
+        for (size_t i = 0; i < S; ++i) {
+            const Shard& sh = d->shards[i];
+            posts.push_back({sh.rank, (int)((uint64_t)sh.rank ^ r.x_rank), w.lam[i], sh.sendbuf, 1ull << L});
+        }
+        post_transfers(d, posts, "Pauli gradient lambda shard send/recv");
+        QSIM_HIPCHK(hipEventRecord(d->events[2], d->comm_stream));
+    }
+    QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[1], 0));
+    for (size_t i = 0; i < S; ++i)
+        launch_dist_pauli_rot(w.phi[i], d->shards[i].recvbuf, w.lam[i], L, r, d->shards[i].rank, true, !last,
+                              d->d_partials, slots + i, d->stream, &d->timer);
+    if (last) return;
+    QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[2], 0));
+    for (size_t i = 0; i < S; ++i)
+        launch_dist_pauli_rot(w.lam[i], d->shards[i].sendbuf, nullptr, L, r, d->shards[i].rank, true, true,
+                              d->d_partials, nullptr, d->stream, &d->timer);
+}
+
+// The value and the sweep of qsim_dist_pauli_gradient, on the state the sequence left.  Rotations
+// never change the map: no segments, no remaps, the work map stays the state's.
+void pauli_gradient_dist(qsim_dist* d, const DistPauliRotPlan& plan, const qsim_pauli_term* terms, size_t nterms,
+                         double* value, double* grad) {
+    const size_t S = d->shards.size(), P = plan.rots.size();
+    *value = 0.0;
+    for (size_t k = 0; k < P; ++k) grad[k] = 0.0;
+    const DistApplyPlan ap = lower_dist_apply(d->n, d->L, terms, nterms, d->perm.data());
+    if (ap.all.terms.empty()) {  // H = 0 (no terms, or every coefficient cancels): no sweep
+        stream_wait(d, d->stream);
+        return;
+    }
+    // (the work shards first: a failed allocation leaves nothing queued)
+    qsim_dist::GradWork* wp = P ? &ensure_grad(d, P) : nullptr;
+    *value = expectation_dist(d, terms, nterms);
+    if (!wp) return;
+    qsim_dist::GradWork& w = *wp;
+    const double sent_before = d->sent_bytes;  // (remapBytes() stays the last run's)
+    grad_load_work(d, w, ap);
+    // the sweep: slot [rotation k][shard i], every rotation its own step, last to first
+    QSIM_HIPCHK(hipMemsetAsync(w.d_slots, 0, P * (S + 1) * sizeof(double), d->stream));
+    for (size_t k = P; k-- > 0;) pauli_grad_step(d, w, plan.rots[k], w.d_slots + k * S, k == 0);
+    grad_reduce(d, w, P, grad);
+    d->sent_bytes = sent_before;
+}
+
+// Host-only mirror of pauli_rotations_dist (qsim_dist_pauli_rotation_plan).
+void pauli_rotation_info(const DistPauliRotPlan& plan, int L, qsim_dist_pauli_rotation_info* out) {
+    std::memset(out, 0, sizeof(*out));
+    out->rotations = (int32_t)plan.rots.size();
+    out->phase_rotations = (int32_t)plan.phase;
+    out->phase_passes = (int32_t)plan.phase_passes;
+    out->local_rotations = (int32_t)plan.local;
+    out->cross_rotations = (int32_t)plan.cross;
+    out->cross_pure = (int32_t)plan.cross_pure;
+    out->launches = (int32_t)plan.launches;
+    out->transfers = (int32_t)plan.cross;
+    out->bytes_sent_per_rank = (uint64_t)plan.cross * ((uint64_t)sizeof(double2) << L);
+}
+
+std::vector<int> checked_perm(int n, const int32_t* perm) {
+    std::vector<int> p(n);
+    uint64_t seen = 0;
+    for (int q = 0; q < n; ++q) {
+        p[q] = perm ? perm[q] : q;
+        if (p[q] < 0 || p[q] >= n || ((seen >> p[q]) & 1ull)) fail(QSIM_ERR_INVALID_ARGUMENT, "qubit map is not a permutation");
+        seen |= 1ull << p[q];
+    }
+    return p;
 }
 }  // namespace
 
@@ -3281,15 +3453,91 @@ int qsim_dist_gradient_plan(int n_qubits, int world, const int32_t* perm, const 
         const int g = log2_exact(world);
         check_sizes(n_qubits, g);
         check_gradient_args(n_qubits, gates, count, terms, nterms);
-        std::vector<int> p(n_qubits);
-        uint64_t seen = 0;
-        for (int q = 0; q < n_qubits; ++q) {
-            p[q] = perm ? perm[q] : q;
-            if (p[q] < 0 || p[q] >= n_qubits || ((seen >> p[q]) & 1ull))
-                fail(QSIM_ERR_INVALID_ARGUMENT, "qubit map is not a permutation");
-            seen |= 1ull << p[q];
-        }
-        gradient_plan_host(n_qubits, g, p, gates, count, terms, nterms, out);
+        gradient_plan_host(n_qubits, g, checked_perm(n_qubits, perm), gates, count, terms, nterms, out);
+    });
+}
+
+int qsim_dist_apply_pauli_rotations(qsim_dist* d, const qsim_pauli_term* rots, size_t count) {
+    return dguard_comm(d, [&] {
+        need(d);
+        if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        if (count == 0) return;
+        // (the lowering checks every mask of the sequence: nothing is launched or posted before)
+        const DistPauliRotPlan plan = lower_dist_pauli_rotations(d->n, d->L, rots, count, d->perm.data());
+        QSIM_HIPCHK(hipSetDevice(d->device));
+        flush_carry(d);  // (the previous run's last step, if it was left pending)
+        d->fresh = false;
+        pauli_rotations_dist(d, plan);
+    });
+}
+
+int qsim_dist_pauli_rotation_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* rots,
+                                  size_t count, qsim_dist_pauli_rotation_info* out) {
+    return dguard([&] {
+        if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
+        const int g = log2_exact(world);
+        check_sizes(n_qubits, g);
+        if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        const std::vector<int> p = checked_perm(n_qubits, perm);
+        pauli_rotation_info(lower_dist_pauli_rotations(n_qubits, n_qubits - g, rots, count, p.data()), n_qubits - g, out);
+    });
+}
+
+int qsim_dist_pauli_gradient(qsim_dist* d, const qsim_pauli_term* rots, size_t count, const qsim_pauli_term* terms,
+                             size_t nterms, double* value, double* grad) {
+    int rc = dguard([&] {
+        need(d);
+        if (!value) fail(QSIM_ERR_INVALID_ARGUMENT, "null value");
+        if (!grad && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gradient");
+        if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        if (!terms && nterms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        // (the observable before the sequence is applied; the sequence's masks: by that call)
+        check_pauli_masks(d->n, terms, nterms, "Pauli term");
+    });
+    if (rc != QSIM_OK) return rc;
+    // The forward pass is qsim_dist_apply_pauli_rotations itself: the state ends exactly as that
+    // call alone leaves it, and nothing below writes to it.
+    if ((rc = qsim_dist_apply_pauli_rotations(d, rots, count)) != QSIM_OK) return rc;
+    return dguard_comm(d, [&] {
+        QSIM_HIPCHK(hipSetDevice(d->device));
+        flush_carry(d);  // (count == 0: nothing above has flushed)
+        const DistPauliRotPlan plan = lower_dist_pauli_rotations(d->n, d->L, rots, count, d->perm.data());
+        pauli_gradient_dist(d, plan, terms, nterms, value, grad);
+    });
+}
+
+int qsim_dist_pauli_gradient_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* rots,
+                                  size_t count, const qsim_pauli_term* terms, size_t nterms,
+                                  qsim_dist_pauli_gradient_info* out) {
+    return dguard([&] {
+        if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
+        const int g = log2_exact(world);
+        check_sizes(n_qubits, g);
+        if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        if (!terms && nterms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        check_pauli_masks(n_qubits, terms, nterms, "Pauli term");
+        const int L = n_qubits - g;
+        const std::vector<int> p = checked_perm(n_qubits, perm);
+        const DistPauliRotPlan plan = lower_dist_pauli_rotations(n_qubits, L, rots, count, p.data());
+        const DistApplyPlan ap = lower_dist_apply(n_qubits, L, terms, nterms, p.data());
+        std::memset(out, 0, sizeof(*out));
+        pauli_rotation_info(plan, L, &out->forward);
+        out->first_class = -1;
+        out->bytes_sent_per_rank = out->forward.bytes_sent_per_rank;
+        if (ap.all.terms.empty() || plan.rots.empty()) return;  // no sweep
+        out->apply_groups_local = (int32_t)ap.local_groups;
+        out->apply_groups_cross = (int32_t)ap.cross_groups;
+        out->apply_transfers = (int32_t)ap.transfers;
+        out->apply_launches = (int32_t)ap.launches;
+        out->steps = (int32_t)plan.rots.size();
+        out->steps_phase = (int32_t)plan.phase;
+        out->steps_local = (int32_t)plan.local;
+        out->steps_cross = (int32_t)plan.cross;
+        out->first_class = plan.rots.front().cls;
+        // (phi and lambda per cross step; the sequence's first rotation needs phi alone)
+        out->step_transfers = (int32_t)(2 * plan.cross) - (plan.rots.front().cls == DPR_CROSS ? 1 : 0);
+        out->bytes_sent_per_rank +=
+            (uint64_t)(out->apply_transfers + out->step_transfers) * ((uint64_t)sizeof(double2) << L);
     });
 }
 

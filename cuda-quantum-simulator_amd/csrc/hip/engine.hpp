@@ -714,9 +714,48 @@ void launch_pauli_phase(double2* st, int n, const ExpectTerm* d_terms, size_t co
 // The whole plan on st; terms: the owner's device copy of the x == 0 runs' tables (one upload).
 void launch_pauli_rotations(double2* st, int n, const PauliRotPlan& plan, DevBuf& terms, hipStream_t s, Timer* tm);
 // *d_out = Im <lam| P |phi>, then (apply) exp(+i theta/2 P) on both states, in one launch; without
-// apply nothing is stored: the bra-ket alone.  d_partials: expect_chunks(1) doubles.
+// apply nothing is stored: the bra-ket alone.  d_partials: expect_chunks(1) doubles.  negate: the
+// generator is -P (a shard on which the string's rank factors give -1), folded in on the host.
 void launch_pauli_adjoint_step(double2* phi, double2* lam, int n, const PauliRot& r, bool apply, double* d_partials,
-                               double* d_out, hipStream_t s, Timer* tm);
+                               double* d_out, hipStream_t s, Timer* tm, bool negate = false);
+
+// Pauli-string rotations on a sharded state (dist_pauli_rot.hip; the transfers and collectives
+// around them: dist.hip).  A rotation's physical masks split as x = x_loc | x_rank << L, z alike.
+enum {
+    DPR_PHASE = 0,  // x == 0: part of a run of Z/I-only rotations, pauli_phase on each shard
+    DPR_LOCAL = 1,  // x_rank == 0, x_loc != 0: pauli_rot on each shard
+    DPR_CROSS = 2   // x_rank != 0: rank r pairs with r ^ x_rank, one whole-shard transfer
+};
+struct DistPauliRot {
+    int cls;
+    uint64_t x_loc, z_loc, x_rank, z_rank;
+    double theta;
+    int ny;  // popcount(x & z) over all n positions
+};
+struct DistPauliRotPlan {
+    std::vector<DistPauliRot> rots;  // application order
+    size_t phase = 0, local = 0, cross = 0, cross_pure = 0;  // rotations by class; cross with x_loc == 0
+    size_t phase_passes = 0;                                 // maximal runs of consecutive phase rotations
+    size_t launches = 0;                                     // kernel launches per shard
+};
+// lower_pauli_rotations over the n physical positions (its checks and errors), then the split.
+DistPauliRotPlan lower_dist_pauli_rotations(int n, int L, const qsim_pauli_term* rots, size_t count, const int* perm);
+// The sign of P's rank factors on shard `rank`, for the classes that read the shard itself (phase,
+// local: (-1)^popcount(rank & z_rank)) and for a cross rotation, which reads rank ^ x_rank's.
+inline bool dist_pauli_rank_neg(const DistPauliRot& r, int rank) {
+    return __builtin_popcountll(((uint64_t)rank ^ r.x_rank) & r.z_rank) & 1;
+}
+// A phase or local rotation as shard `rank` runs it with n = L: the rank sign folded into theta.
+PauliRot dist_pauli_shard_rot(const DistPauliRot& r, int rank);
+// A cross rotation on one shard, peer = the whole old shard of rank ^ x_rank.  With
+// (P v)_own[i] = g sg(i) peer[i ^ x_loc], sg(i) = (-1)^popcount((i ^ x_loc) & z_loc), g = i^nY times
+// the rank sign:  own[i] <- cos(theta/2) own[i] + (-+) i sin(theta/2) (P v)_own[i], - forward,
+// + adjoint (the sweep's U^†).  lam != null (own = phi): first *d_out = this rank's share of
+// Im <lam| P |phi>; store = false (needs lam): that alone, nothing is written.  d_partials:
+// expect_chunks(1) doubles.  Asynchronous.
+void launch_dist_pauli_rot(double2* own, const double2* peer, const double2* lam, int L, const DistPauliRot& r,
+                           int rank, bool adjoint, bool store, double* d_partials, double* d_out, hipStream_t s,
+                           Timer* tm);
 
 // Adjoint-method gradients on a sharded state (dist_adjoint.hip; the transfers, the inverted
 // segments and the collectives around it: dist.hip).

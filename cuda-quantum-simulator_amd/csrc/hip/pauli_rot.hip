@@ -246,16 +246,27 @@ void launch_pauli_rotations(double2* st, int n, const PauliRotPlan& plan, DevBuf
 }
 
 void launch_pauli_adjoint_step(double2* phi, double2* lam, int n, const PauliRot& r, bool apply, double* d_partials,
-                               double* d_out, hipStream_t s, Timer* tm) {
+                               double* d_out, hipStream_t s, Timer* tm, bool negate) {
     check_masks(n, r);
     const uint64_t N = 1ull << n;
     const bool pair = r.x != 0;
     const uint64_t count = pair ? N >> 1 : N;
     const uint64_t lomask = pair ? (1ull << (63 - __builtin_clzll(r.x))) - 1ull : 0ull;
     const int ny = __builtin_popcountll(r.x & r.z);
-    const double2 gj = i_pow(ny);
+    double2 gj = i_pow(ny);
+    double c = std::cos(0.5 * r.theta), sn = std::sin(0.5 * r.theta);  // U^† = c + i sn P
+    if (negate) {
+        // Generator -P.  Pair form: the sign goes into the two weights of P.  Amplitude form (no
+        // weights): Im <phi|P|lam> = -Im <lam|P|phi> and both states get the same update, so the
+        // states swap roles and the update's angle flips.
+        if (pair) {
+            gj = make_double2(-gj.x, -gj.y);
+        } else {
+            std::swap(phi, lam);
+            sn = -sn;
+        }
+    }
     const double2 gi = ny & 1 ? make_double2(-gj.x, -gj.y) : gj;
-    const double c = std::cos(0.5 * r.theta), sn = std::sin(0.5 * r.theta);  // U^† = c + i sn P
     const unsigned chunks = (unsigned)std::min<uint64_t>((count + 255) / 256, expect_chunks(1));
     auto kernel = pair ? (apply ? k_pauli_adjoint_step<true, true> : k_pauli_adjoint_step<true, false>)
                        : (apply ? k_pauli_adjoint_step<false, true> : k_pauli_adjoint_step<false, false>);

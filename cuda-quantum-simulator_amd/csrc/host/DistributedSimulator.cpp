@@ -125,6 +125,38 @@ void DistributedSimulator::releaseGradientBuffers() {
     check(qsim_dist_gradient_release(h_));
 }
 
+namespace {
+std::vector<qsim_pauli_term> termsOf(const PauliSum& p, int n, const char* what) {
+    if (p.getNumQubits() != n) throw std::invalid_argument(std::string(what) + " qubit count doesn't match simulator");
+    std::vector<qsim_pauli_term> out;
+    out.reserve(p.size());
+    for (const PauliSum::Term& t : p.terms()) out.push_back(qsim_pauli_term{t.x_mask, t.z_mask, t.coeff});
+    return out;
+}
+}  // namespace
+
+void DistributedSimulator::applyPauliRotation(const std::vector<std::pair<int, char>>& factors, double theta) {
+    applyPauliRotations(PauliSum(num_qubits_).add(theta, factors));
+}
+
+void DistributedSimulator::applyPauliRotations(const PauliSum& seq) {
+    const std::vector<qsim_pauli_term> rots = termsOf(seq, num_qubits_, "Rotation sequence");
+    check(qsim_dist_apply_pauli_rotations(h_, rots.data(), rots.size()));
+}
+
+void DistributedSimulator::evolve(const PauliSum& H, double time, int steps, int order) {
+    applyPauliRotations(trotter_sequence(H, time, steps, order));
+}
+
+Gradient DistributedSimulator::pauliGradient(const PauliSum& seq, const PauliSum& observable) {
+    const std::vector<qsim_pauli_term> rots = termsOf(seq, num_qubits_, "Rotation sequence");
+    const std::vector<qsim_pauli_term> terms = termsOf(observable, num_qubits_, "Observable");
+    Gradient g{0.0, std::vector<double>(rots.size(), 0.0)};
+    check(qsim_dist_pauli_gradient(h_, rots.data(), rots.size(), terms.data(), terms.size(), &g.value,
+                                   g.gradient.data()));
+    return g;
+}
+
 void DistributedSimulator::setSeed(unsigned int seed) {
     rng_.seed(seed);
     seeded_ = true;

@@ -272,6 +272,27 @@ _sig(hip, "qsim_dist_gradient_release", [_P])
 _sig(hip, "qsim_dist_gradient_memory_bytes", [_P, POINTER(c_uint64)])
 _sig(hip, "qsim_dist_gradient_plan", [c_int, c_int, POINTER(c_int32), POINTER(qsim_gate), c_size_t,
                                       POINTER(qsim_pauli_term), c_size_t, POINTER(qsim_dist_gradient_info)])
+class qsim_dist_pauli_rotation_info(Structure):
+    _fields_ = [(k, c_int32) for k in (
+        "rotations", "phase_rotations", "phase_passes", "local_rotations", "cross_rotations", "cross_pure",
+        "launches", "transfers")] + [("bytes_sent_per_rank", c_uint64)]
+
+
+class qsim_dist_pauli_gradient_info(Structure):
+    _fields_ = [("forward", qsim_dist_pauli_rotation_info)] + [(k, c_int32) for k in (
+        "steps", "steps_phase", "steps_local", "steps_cross", "first_class", "apply_groups_local",
+        "apply_groups_cross", "apply_transfers", "apply_launches", "step_transfers")] + [
+        ("bytes_sent_per_rank", c_uint64)]
+
+
+_sig(hip, "qsim_dist_apply_pauli_rotations", [_P, POINTER(qsim_pauli_term), c_size_t])
+_sig(hip, "qsim_dist_pauli_rotation_plan", [c_int, c_int, POINTER(c_int32), POINTER(qsim_pauli_term), c_size_t,
+                                            POINTER(qsim_dist_pauli_rotation_info)])
+_sig(hip, "qsim_dist_pauli_gradient", [_P, POINTER(qsim_pauli_term), c_size_t, POINTER(qsim_pauli_term), c_size_t,
+                                       POINTER(c_double), POINTER(c_double)])
+_sig(hip, "qsim_dist_pauli_gradient_plan", [c_int, c_int, POINTER(c_int32), POINTER(qsim_pauli_term), c_size_t,
+                                            POINTER(qsim_pauli_term), c_size_t,
+                                            POINTER(qsim_dist_pauli_gradient_info)])
 _sig(hip, "qsim_dist_sample_plan", [c_int, c_int, POINTER(c_int32), POINTER(c_int), POINTER(c_uint64)])
 _sig(hip, "qsim_dist_profile", [_P, c_int])
 _sig(hip, "qsim_dist_profile_count", [_P, POINTER(c_int)])

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import _lib
 from .circuit import Circuit
+from .observable import PauliSum, trotter_sequence
 
 _c = ctypes
 UNIQUE_ID_BYTES = 128
@@ -216,6 +217,43 @@ class DistributedSimulator:
             _c.byref(value), grad.ctypes.data_as(_c.POINTER(_c.c_double))))
         return value.value, grad[:cnt]
 
+    # Pauli-string rotations on the sharded state (collective; Simulator's signatures and exceptions)
+    def applyPauliRotation(self, factors, theta: float) -> None:
+        """exp(-i theta/2 P) in place, P the product of the factors {qubit: 'X' | 'Y' | 'Z'} (as
+        PauliSum.add takes them; none: the global phase).  IndexError on a bad qubit, before
+        anything is applied."""
+        self.applyPauliRotations(PauliSum(self._n).add(theta, factors))
+
+    def applyPauliRotations(self, seq) -> None:
+        """A PauliSum read as an ordered sequence: term t is exp(-i coeff_t/2 P_t), applied in
+        add() order where the shards lie (qsim_dist_apply_pauli_rotations): no remap, perm()
+        unchanged.  A run of consecutive Z/I-only rotations is one pass per shard; a rotation with
+        X or Y factors on local positions only is one pass per shard; one with an X or Y factor on
+        a qubit that sits on a rank position pairs each rank with one peer and moves a whole
+        shard each way.  ValueError on a qubit-count mismatch."""
+        rots, count = seq.to_abi(self._n)
+        _lib.check(_lib.hip.qsim_dist_apply_pauli_rotations(self._h, rots, count))
+
+    def evolve(self, H, time: float, steps: int = 1, order: int = 1) -> None:
+        """The Trotter product for exp(-i H time) on the state as it is: nothing but
+        applyPauliRotations(trotter_sequence(H, time, steps, order)).  ValueError when steps < 1,
+        order is not 1 or 2 or the qubit counts differ."""
+        self.applyPauliRotations(trotter_sequence(H, time, steps, order))
+
+    def pauliGradient(self, seq, observable):
+        """(value, gradient) as Simulator.pauliGradient, on the sharded state (collective,
+        qsim_dist_pauli_gradient): applies `seq` as applyPauliRotations does, then <psi|H|psi> and
+        its derivative with respect to the angle of every rotation by one backward sweep over the
+        two sharded work states of gradient() (releaseGradientBuffers frees them).  The state is
+        left as applyPauliRotations(seq) leaves it; every rank gets the same floats."""
+        rots, count = seq.to_abi(self._n)
+        terms, nterms = observable.to_abi(self._n)
+        value = _c.c_double()
+        grad = np.zeros(max(1, count), dtype=np.float64)
+        _lib.check(_lib.hip.qsim_dist_pauli_gradient(self._h, rots, count, terms, nterms, _c.byref(value),
+                                                     grad.ctypes.data_as(_c.POINTER(_c.c_double))))
+        return value.value, grad[:count]
+
     def releaseGradientBuffers(self) -> None:
         """Free the two work shards per rank gradient() keeps between calls."""
         _lib.check(_lib.hip.qsim_dist_gradient_release(self._h))
@@ -381,6 +419,57 @@ def gradient_plan(circuit: Circuit, world: int, observable, perm: Optional[List[
     out["perm_after_run"] = list(info.perm_after_run[:n])
     out["perm_after_sweep"] = list(info.perm_after_sweep[:n])
     return out
+
+
+def _terms_arg(n: int, items):
+    """A PauliSum, or a list of (x_mask, z_mask, coeff), as the ABI's term array and its count."""
+    if hasattr(items, "to_abi"):
+        return items.to_abi(n)
+    items = list(items)
+    terms = (_lib.qsim_pauli_term * max(1, len(items)))()
+    for i, (x, z, c) in enumerate(items):
+        terms[i].x_mask, terms[i].z_mask, terms[i].coeff = x, z, c
+    return terms, len(items)
+
+
+def _info_dict(info) -> dict:
+    out = {}
+    for k, _ in info._fields_:
+        v = getattr(info, k)
+        if hasattr(v, "_fields_"):
+            out.update({f"{k}_{kk}": vv for kk, vv in _info_dict(v).items()})
+        else:
+            out[k] = v
+    return out
+
+
+def pauli_rotation_plan(n: int, world: int, perm: Optional[List[int]], seq) -> dict:
+    """Host-only (qsim_dist_pauli_rotation_plan): what DistributedSimulator.applyPauliRotations
+    does for a sequence (a PauliSum, or a list of (x_mask, z_mask, theta)) under qubit map `perm`
+    (None: the identity): {rotations, phase_rotations, phase_passes, local_rotations,
+    cross_rotations, cross_pure, launches, transfers, bytes_sent_per_rank}."""
+    if perm is not None and len(perm) != n:
+        raise ValueError("perm needs one entry per qubit")
+    rots, count = _terms_arg(n, seq)
+    p = (_c.c_int32 * n)(*perm) if perm is not None else None
+    info = _lib.qsim_dist_pauli_rotation_info()
+    _lib.check(_lib.hip.qsim_dist_pauli_rotation_plan(n, world, p, rots, count, _c.byref(info)))
+    return _info_dict(info)
+
+
+def pauli_gradient_plan(n: int, world: int, perm: Optional[List[int]], seq, observable) -> dict:
+    """Host-only (qsim_dist_pauli_gradient_plan): what DistributedSimulator.pauliGradient does
+    under qubit map `perm` (None: the identity): the application's figures as forward_*, the
+    sweep's steps by class, the class of the bra-ket-only step (first_class), the groups and
+    transfers of lambda = H phi, the steps' transfers and the bytes one rank sends."""
+    if perm is not None and len(perm) != n:
+        raise ValueError("perm needs one entry per qubit")
+    rots, count = _terms_arg(n, seq)
+    terms, nterms = _terms_arg(n, observable)
+    p = (_c.c_int32 * n)(*perm) if perm is not None else None
+    info = _lib.qsim_dist_pauli_gradient_info()
+    _lib.check(_lib.hip.qsim_dist_pauli_gradient_plan(n, world, p, rots, count, terms, nterms, _c.byref(info)))
+    return _info_dict(info)
 
 
 def plan_memo_clear() -> None:

@@ -63,6 +63,22 @@ public:
     Gradient gradient(const Circuit& circuit, const PauliSum& observable, RunMode mode = RunMode::Fused);
     void releaseGradientBuffers();  // free the two work shards per rank gradient() keeps between calls
 
+    // Simulator's Pauli-string rotations on the sharded state (collective,
+    // qsim_dist_apply_pauli_rotations): exp(-i theta/2 P) in add() order where the shards lie, no
+    // remap and the qubit map unchanged.  A run of consecutive Z/I-only rotations is one pass per
+    // shard, a rotation with X or Y factors on local positions only one pass per shard; one with an
+    // X or Y factor on a qubit that sits on a rank position pairs each rank with one peer and moves
+    // a whole shard each way.  Exceptions as on Simulator.
+    void applyPauliRotation(const std::vector<std::pair<int, char>>& factors, double theta);
+    void applyPauliRotations(const PauliSum& seq);
+    // applyPauliRotations(trotter_sequence(H, time, steps, order)).
+    void evolve(const PauliSum& H, double time, int steps = 1, int order = 1);
+    // Simulator::pauliGradient on the sharded state (collective, qsim_dist_pauli_gradient): applies
+    // `seq`, then <psi|H|psi> and its derivative with respect to every rotation's angle by one
+    // backward sweep over the work shards of gradient().  The same values on every rank; the state
+    // is left as applyPauliRotations(seq) leaves it.
+    Gradient pauliGradient(const PauliSum& seq, const PauliSum& observable);
+
     std::vector<int> sample(int n_shots);  // without collapse; the same shots on every rank
     int measureQubit(int qubit);           // reference semantics: index bit n-1-qubit (F2)
 

@@ -746,6 +746,84 @@ typedef struct qsim_dist_gradient_info {
 } qsim_dist_gradient_info;
 int qsim_dist_gradient_plan(int n_qubits, int world, const int32_t* perm, const qsim_gate* gates, size_t count,
                             const qsim_pauli_term* terms, size_t nterms, qsim_dist_gradient_info* out);
+/* qsim_state_apply_pauli_rotations on the sharded state (collective): term t of `rots` is
+ * exp(-i coeff_t/2 P_t), applied in order where the state lies.  The masks are mapped through the
+ * qubit map on the host; no remap ever runs for a rotation and qsim_dist_perm, the run getters,
+ * the cached run plans and the gradient work shards are left as they are (a carried step is
+ * flushed first, as by every entry that changes the state).  With L = n - log2 world local
+ * positions the physical masks split as x = x_loc | x_rank << L, z alike, and the z bits on rank
+ * positions are a sign that is constant on a shard and folded in on the host.  Classes:
+ *   phase (x == 0): a maximal run of consecutive Z/I-only rotations is one pass per shard (one
+ *     launch per 256 rotations), each shard with its own signed angle table; no transfer;
+ *   local (x_rank == 0, x_loc != 0): the single-GPU pair kernel on each shard; no transfer;
+ *   cross (x_rank != 0): rank r pairs with the single peer r ^ x_rank; both send their WHOLE old
+ *     shard through the exchange staging buffers (every amplitude is updated, so the half-shard
+ *     transfer of qsim_dist_expectation does not apply), then one kernel writes
+ *     own[i] = cos(theta/2) own[i] + w sg(i) peer[i ^ x_loc]: 32 B read and 16 B written per
+ *     amplitude, 16 B per amplitude and direction over the link.  The shard is overwritten only
+ *     after the transfer that sends it has completed.  x_loc may be 0 (a pure rank flip).
+ * Nothing is reordered or merged beyond Z-only runs.  Every argument of the whole sequence is
+ * checked before the first launch or post, so a bad mask fails on all ranks alike: a mask bit >= n
+ * -> QSIM_ERR_OUT_OF_RANGE, null rots with count > 0 -> QSIM_ERR_INVALID_ARGUMENT, the state
+ * untouched.  count == 0 does nothing.  QSIM_PAULI_BLOCKS caps the work-groups of all three
+ * streaming kernels.  A world of one runs exactly the launches of qsim_state_apply_pauli_rotations.
+ * Asynchronous on virtual ranks and RCCL; the hosted transport completes each transfer on the host. */
+int qsim_dist_apply_pauli_rotations(qsim_dist* d, const qsim_pauli_term* rots, size_t count);
+/* Host-only: what the call above would do for qubit map `perm` (n entries; null: the identity) in
+ * a world of `world` ranks.  A transfer moves one whole shard (16 << (n - log2 world) bytes). */
+typedef struct qsim_dist_pauli_rotation_info {
+    int32_t rotations;        /* count */
+    int32_t phase_rotations;  /* x == 0 */
+    int32_t phase_passes;     /* maximal runs of them: one pass over each shard per run */
+    int32_t local_rotations;  /* x_rank == 0, x_loc != 0 */
+    int32_t cross_rotations;  /* x_rank != 0 */
+    int32_t cross_pure;       /* ... of which x_loc == 0 */
+    int32_t launches;         /* kernel launches per shard */
+    int32_t transfers;        /* whole-shard transfers: one per cross rotation */
+    uint64_t bytes_sent_per_rank;
+} qsim_dist_pauli_rotation_info;
+int qsim_dist_pauli_rotation_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* rots,
+                                  size_t count, qsim_dist_pauli_rotation_info* out);
+/* qsim_state_pauli_gradient on the sharded state (collective).  Applies the sequence exactly as
+ * qsim_dist_apply_pauli_rotations does, then *value = <psi|H|psi> as qsim_dist_expectation computes
+ * it and grad[k] = dE/dtheta_k for k < count by one backward sweep over the two sharded work
+ * states of qsim_dist_gradient (the same buffers: counted by qsim_dist_gradient_memory_bytes, freed
+ * by qsim_dist_gradient_release), phi copied from the state and lambda = H phi built as there.
+ * Rotations never change the qubit map, so the sweep has no segments and no remaps.  One step per
+ * rotation, last to first (Z-only runs are not merged in the sweep):
+ *   phase and local: the single-GPU step on each shard (Im <lambda|P|phi>, then exp(+i theta/2 P)
+ *     on both work states in one launch), the shard's rank sign folded in on the host;
+ *   cross: the rank receives the peer's whole old phi shard, then its old lambda shard (the second
+ *     transfer in flight while the first kernel runs); launch 1 adds this rank's share of
+ *     Im conj(lambda_own)(P phi)_own and updates phi_own, launch 2 updates lambda_own.  The two
+ *     ranks' shares add up to the whole bra-ket.
+ * The sweep's last step, the sequence's first rotation, is the bra-ket alone: a cross step there
+ * needs the peer's phi only and stores nothing.  No floating-point atomics: every (rotation, shard)
+ * sum has a slot of its own, the shards of a process are added in rank order and ONE vector
+ * all-reduce adds the ranks, so every rank returns the same doubles and two calls return
+ * bitwise-equal results.  The sweep never writes the state's shards: the state ends exactly as
+ * qsim_dist_apply_pauli_rotations alone leaves it.  count == 0: *value = <H> of the state as it is;
+ * nterms == 0 or H == 0: value 0, zero gradient, no sweep, no allocation.  Every argument is checked
+ * before the sequence is applied (the codes of the apply call; a mask bit >= n of the observable ->
+ * QSIM_ERR_OUT_OF_RANGE); work shards that cannot be allocated -> QSIM_ERR_DEVICE with the state
+ * holding the rotated state.  Synchronises. */
+int qsim_dist_pauli_gradient(qsim_dist* d, const qsim_pauli_term* rots, size_t count, const qsim_pauli_term* terms,
+                             size_t nterms, double* value, double* grad);
+/* Host-only: what qsim_dist_pauli_gradient would do under qubit map `perm` (null: the identity).
+ * bytes_sent_per_rank = (forward.transfers + apply_transfers + step_transfers) whole shards. */
+typedef struct qsim_dist_pauli_gradient_info {
+    qsim_dist_pauli_rotation_info forward; /* the sequence's application */
+    int32_t steps;            /* steps of the sweep: count, or 0 when H == 0 (no sweep) */
+    int32_t steps_phase, steps_local, steps_cross; /* ... by class */
+    int32_t first_class;      /* class of the sequence's first rotation, the bra-ket-only step:
+                                 0 phase, 1 local, 2 cross; -1 without a sweep */
+    int32_t apply_groups_local, apply_groups_cross, apply_transfers, apply_launches; /* lambda = H phi */
+    int32_t step_transfers;   /* whole-shard transfers of the cross steps: 2 each, 1 for the first rotation */
+    uint64_t bytes_sent_per_rank;
+} qsim_dist_pauli_gradient_info;
+int qsim_dist_pauli_gradient_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* rots,
+                                  size_t count, const qsim_pauli_term* terms, size_t nterms,
+                                  qsim_dist_pauli_gradient_info* out);
 /* Host-only: what qsim_dist_sample would do for qubit map `perm` (n entries): the chunk size
  * (log2) and the set of logical qubits it must bring local first (0: no remap). */
 int qsim_dist_sample_plan(int n_qubits, int world, const int32_t* perm, int* chunk_log,

@@ -583,6 +583,38 @@ void launch_expectation(const double2* st, int n, uint64_t batch, const ExpectPl
 constexpr int kExpectSplitMin = 16;
 bool expect_split_on();
 
+// Marginal probabilities and reduced density matrices of k qubits (marginal.hip).  The listed
+// qubits are mapped to physical positions through perm (null: identity); positions below the run
+// (c = min(n, kMarginalRunBits) bits) are binned inside a work-group, those above choose its runs.
+constexpr int kMarginalMaxQubits = 20;   // 2^20 bins
+constexpr int kRdmMaxQubits = 6;         // a 64 x 64 matrix
+constexpr int kMarginalRunBits = 12;     // 4096 contiguous amplitudes, 16 per thread
+constexpr int kMarginalGroupsLog = 12;   // work-groups aimed at when the state has that many runs
+constexpr int kMarginalScratchLog = 26;  // partial sums never take more than 64 MiB
+constexpr uint64_t kRdmGroups = 1024;    // work-groups (and partial matrices) of the matrix kernel
+struct MarginalPlan {
+    int n = 0, k = 0, c = 0;
+    bool rdm = false;
+    uint64_t sel = 0;        // selected physical positions
+    int k_lo = 0, k_hi = 0;  // ... below / from position c
+    unsigned slices = 1;     // marginal: slices of the unselected high bits; matrix: = groups
+    uint64_t groups = 1;     // work-groups of the first kernel
+    uint64_t scratch_bytes = 0;
+    int launches = 0;
+    std::vector<int> dst;    // bit i of a kernel-side index (ascending position) -> the caller's bit
+};
+// Throws Error: a duplicate qubit, k above the reader's cap or above n, a null list with k > 0, a
+// perm that is no permutation (invalid argument); a qubit outside [0, n) (out of range).
+MarginalPlan lower_marginal(int n, const int32_t* qubits, int k, const int* perm, bool rdm);
+// d_out: 2^k doubles in the caller's bit order (marginal), or 2 * 4^k doubles of rho numbered by
+// ascending physical position (matrix; rdm_finish makes the caller's matrix of it on the host).
+// d_partials: plan.scratch_bytes.  Reads st only.  Asynchronous.
+void launch_marginal(const double2* st, const MarginalPlan& plan, double* d_partials, double* d_out, hipStream_t s,
+                     Timer* tm);
+// Host: the upper triangle of raw in the caller's numbering, the diagonal's imaginary part zeroed,
+// mirrored into the lower one (out == out^dagger bitwise).
+void rdm_finish(const MarginalPlan& plan, const double* raw, double* out);
+
 // Pauli-sum expectation values Re Tr(rho H) of a density matrix (dm_expect.hip).  Terms are merged
 // and grouped by logical x mask (one generalised diagonal of rho, 2^n elements, per group) and a
 // group is cut into rows of at most kExpectTerms terms with complex weights c i^nY (cr + i ci, z:

@@ -140,6 +140,9 @@ _sig(hip, "qsim_state_expectation", [_P, POINTER(qsim_pauli_term), c_size_t, POI
 _sig(hip, "qsim_batch_expectation", [_P, POINTER(qsim_pauli_term), c_size_t, POINTER(c_double)])
 _sig(hip, "qsim_expectation_plan", [c_int, POINTER(qsim_pauli_term), c_size_t, POINTER(c_int32), POINTER(c_int),
                                     POINTER(c_int)])
+_sig(hip, "qsim_state_marginal_probabilities", [_P, POINTER(c_int32), c_int, _P])
+_sig(hip, "qsim_state_reduced_density_matrix", [_P, POINTER(c_int32), c_int, _P])
+_sig(hip, "qsim_marginal_plan", [c_int, POINTER(c_int32), c_int, POINTER(c_int32), c_int, POINTER(c_int32)])
 _sig(hip, "qsim_state_apply_pauli_sum", [_P, _P, POINTER(qsim_pauli_term), c_size_t])
 _sig(hip, "qsim_state_inner_product", [_P, _P, POINTER(c_double)])
 _sig(hip, "qsim_gate_inverse", [POINTER(qsim_gate), POINTER(qsim_gate)])
@@ -319,6 +322,7 @@ _sig(api, "qsim_circuit_depth", [c_int, POINTER(qsim_gate), c_size_t, POINTER(c_
 _sig(api, "qsim_circuits_last_error", [], c_char_p)
 _sig(api, "qsim_pauli_term_make", [c_int, POINTER(c_int32), c_char_p, c_size_t, c_double,
                                    POINTER(qsim_pauli_term)])
+_sig(api, "qsim_hermitian_entropy", [_P, c_int, c_int, POINTER(c_double)])
 
 
 def raise_for(rc: int, msg_fn=None) -> None:

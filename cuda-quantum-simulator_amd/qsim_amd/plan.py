@@ -203,6 +203,34 @@ def pauli_rotation_plan(seq, perm=None):
     return p.value, l.value
 
 
+def marginal_plan(n: int, qubits, perm=None, rdm: bool = False) -> dict:
+    """How marginalProbabilities (rdm: reducedDensityMatrix) of these qubits on an n-qubit state
+    splits its work under the qubit layout perm (logical -> physical; None: identity): k_lo / k_hi
+    selected physical positions below / above a work-group's contiguous run, slices of the
+    unselected high positions, work-groups of the first kernel, scratch bytes of the partial sums
+    and kernel launches (qsim_marginal_plan, host only).  The readers' argument checks."""
+    qs = [int(q) for q in qubits]
+    arr = (ctypes.c_int32 * len(qs))(*qs) if qs else None
+    info = (ctypes.c_int32 * 8)()
+    _lib.check(_lib.hip.qsim_marginal_plan(n, arr, len(qs), _perm_arg(n, perm), 1 if rdm else 0, info))
+    return {"k_lo": info[0], "k_hi": info[1], "slices": info[2], "work_groups": info[3],
+            "scratch_bytes": (info[4] & 0xffffffff) | (info[5] << 32), "launches": info[6]}
+
+
+def hermitian_entropy(rho, renyi2: bool = False) -> float:
+    """The entropy in bits of a density matrix (at most 64 x 64) by the C++ layer's host routine,
+    the cyclic Jacobi sweep behind qsim::StateVector::entanglementEntropy (qsim_hermitian_entropy;
+    host only)."""
+    m = np.ascontiguousarray(rho, dtype=np.complex128)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("rho must be a square matrix")
+    out = ctypes.c_double()
+    _lib.raise_for(_lib.api.qsim_hermitian_entropy(m.ctypes.data_as(ctypes.c_void_p), m.shape[0],
+                                                   1 if renyi2 else 0, ctypes.byref(out)),
+                   lambda: "bad density matrix")
+    return out.value
+
+
 def pauli_gradient_plan(seq, observable, perm=None):
     """(steps of the backward sweep, Pauli-sum apply passes) of Simulator.pauliGradient under the
     qubit layout perm (qsim_pauli_gradient_plan, host only): every rotation its own step, no step

@@ -160,6 +160,49 @@ class StateVector:
         _lib.check(_lib.hip.qsim_state_expectation(self._h, terms, count, _c.byref(e)))
         return e.value
 
+    def _qubit_list(self, qubits, cap: int):
+        qs = [int(q) for q in qubits]
+        if len(qs) > cap:
+            raise ValueError(f"at most {cap} qubits")
+        return (_c.c_int32 * len(qs))(*qs) if qs else None, len(qs)
+
+    def marginalProbabilities(self, qubits) -> np.ndarray:
+        """The 2^k marginal probabilities of k <= 20 distinct qubits (any order; k = 0: the total
+        probability): out[m] = sum of |psi_i|^2 over the i whose bit qubits[j] equals bit j of m.
+        Qubit q is index bit q, the gates' and PauliSum's convention (not measure(q)'s big-endian
+        one).  One streaming read where the state lies: no readback of the amplitudes, no layout
+        restore, bitwise reproducible (qsim_state_marginal_probabilities; no reference
+        counterpart).  ValueError on a duplicate or too many qubits, IndexError on a bad qubit."""
+        arr, k = self._qubit_list(qubits, 20)
+        out = np.empty(1 << k, dtype=np.float64)
+        _lib.check(_lib.hip.qsim_state_marginal_probabilities(self._h, arr, k, _ptr(out)))
+        return out
+
+    def reducedDensityMatrix(self, qubits) -> np.ndarray:
+        """rho_A of k <= 6 qubits as a 2^k x 2^k complex128 array, rho_A[a, a'] = sum_b psi(a, b)
+        conj(psi(a', b)) with bit j of a = qubit qubits[j]; equal to its conjugate transpose
+        bitwise, its diagonal the marginal (qsim_state_reduced_density_matrix).  Reads the state
+        where it lies; errors as marginalProbabilities."""
+        arr, k = self._qubit_list(qubits, 6)
+        out = np.empty((1 << k, 1 << k), dtype=np.complex128)
+        _lib.check(_lib.hip.qsim_state_reduced_density_matrix(self._h, arr, k, _ptr(out)))
+        return out
+
+    def subsystemPurity(self, qubits) -> float:
+        """Tr rho_A^2 of the k <= 6 qubits."""
+        rho = self.reducedDensityMatrix(qubits)
+        return float(np.sum(rho.real ** 2 + rho.imag ** 2))
+
+    def entanglementEntropy(self, qubits, renyi2: bool = False) -> float:
+        """Von Neumann entropy of rho_A in bits, -sum l log2 l over numpy.linalg.eigvalsh(rho_A)
+        (eigenvalues below 1e-300 contribute 0); renyi2: -log2 Tr rho_A^2 instead."""
+        rho = self.reducedDensityMatrix(qubits)
+        if renyi2:
+            return float(-np.log2(np.sum(rho.real ** 2 + rho.imag ** 2)))
+        ev = np.linalg.eigvalsh(rho)
+        ev = ev[ev >= 1e-300]
+        return float(-np.sum(ev * np.log2(ev)))
+
     def applyPauliSum(self, observable, dst: "StateVector") -> None:
         """dst = H |self> out of place on the device (qsim_state_apply_pauli_sum); dst takes this
         state's qubit layout.  ValueError when dst is self or of another size."""
@@ -377,6 +420,12 @@ class Simulator:
     def measureQubit(self, qubit: int) -> int: return self._state.measure(qubit)
     # no reference counterpart: StateVector.expectation
     def expectation(self, observable) -> float: return self._state.expectation(observable)
+    def marginalProbabilities(self, qubits) -> np.ndarray: return self._state.marginalProbabilities(qubits)
+    def reducedDensityMatrix(self, qubits) -> np.ndarray: return self._state.reducedDensityMatrix(qubits)
+    def subsystemPurity(self, qubits) -> float: return self._state.subsystemPurity(qubits)
+
+    def entanglementEntropy(self, qubits, renyi2: bool = False) -> float:
+        return self._state.entanglementEntropy(qubits, renyi2)
 
     def gradient(self, circuit: Circuit, observable, mode: RunMode = RunMode.Fused):
         """(value, gradient): runs `circuit` on the state as it is, as run() would in `mode`, then
@@ -579,6 +628,13 @@ class NoisySimulator:
 
     # no reference counterpart: StateVector.expectation
     def expectation(self, observable) -> float: return self._state.expectation(observable)
+    def marginalProbabilities(self, qubits) -> np.ndarray: return self._state.marginalProbabilities(qubits)
+    def reducedDensityMatrix(self, qubits) -> np.ndarray: return self._state.reducedDensityMatrix(qubits)
+    def subsystemPurity(self, qubits) -> float: return self._state.subsystemPurity(qubits)
+
+    def entanglementEntropy(self, qubits, renyi2: bool = False) -> float:
+        return self._state.entanglementEntropy(qubits, renyi2)
+
     def getNumQubits(self) -> int: return self._state.getNumQubits()
     def getStateSize(self) -> int: return self._state.getSize()
     def synchronize(self) -> None: self._state.synchronize()

@@ -93,6 +93,11 @@ public:
     StateVector& state() { return state_; }
     // <psi|H|psi> of a Pauli sum on the device (no reference counterpart; StateVector::expectation).
     double expectation(const PauliSum& observable) const;
+    // Readout of a subset of qubits on the device (no reference counterpart): StateVector's methods.
+    std::vector<double> marginalProbabilities(const std::vector<int>& qubits) const;
+    std::vector<std::complex<double>> reducedDensityMatrix(const std::vector<int>& qubits) const;
+    double subsystemPurity(const std::vector<int>& qubits) const;
+    double entanglementEntropy(const std::vector<int>& qubits, bool renyi2 = false) const;
 
 private:
     StateVector state_;

@@ -72,6 +72,11 @@ public:
     // applyPauliRotations(seq) leaves it.  The angles are independent parameters: a parameter
     // shared between rotations (a QAOA gamma) is the caller's chain rule over the gradient.
     Gradient pauliGradient(const PauliSum& seq, const PauliSum& observable);
+    // Readout of a subset of qubits on the device (no reference counterpart): StateVector's methods.
+    std::vector<double> marginalProbabilities(const std::vector<int>& qubits) const;
+    std::vector<std::complex<double>> reducedDensityMatrix(const std::vector<int>& qubits) const;
+    double subsystemPurity(const std::vector<int>& qubits) const;
+    double entanglementEntropy(const std::vector<int>& qubits, bool renyi2 = false) const;
 
     int getNumQubits() const { return state_.getNumQubits(); }
     size_t getStateSize() const { return state_.getSize(); }

@@ -83,6 +83,21 @@ public:
     std::complex<double> innerProduct(const StateVector& other) const;
     void assertNormalized(double tolerance = 1e-10) const;  // std::runtime_error
 
+    // Readout of a subset of qubits where the state lies: one streaming read, no readback of the
+    // amplitudes, no layout restore (qsim_state_marginal_probabilities /
+    // qsim_state_reduced_density_matrix; no reference counterpart).  Qubits follow the gates' and
+    // PauliSum's convention, qubit q == index bit q — NOT measure(q)'s big-endian mapping (F2);
+    // they are distinct and in any order, and bit j of an output index is qubits[j].
+    // std::invalid_argument on a duplicate or too many qubits, std::out_of_range on a bad qubit.
+    // 2^k probabilities of the k <= 20 qubits (k = 0: the total probability).
+    std::vector<double> marginalProbabilities(const std::vector<int>& qubits) const;
+    // rho_A of the k <= 6 qubits, 2^k x 2^k row-major, bitwise equal to its conjugate transpose.
+    std::vector<std::complex<double>> reducedDensityMatrix(const std::vector<int>& qubits) const;
+    double subsystemPurity(const std::vector<int>& qubits) const;  // Tr rho_A^2
+    // Von Neumann entropy of rho_A in bits, -sum l log2 l over its eigenvalues (those below 1e-300
+    // contribute 0; a cyclic Jacobi sweep on the host); renyi2: -log2 Tr rho_A^2 instead.
+    double entanglementEntropy(const std::vector<int>& qubits, bool renyi2 = false) const;
+
     // Reference semantics (src/StateVector.cu:260-314): measures index bit n-1-qubit
     // (big-endian), collapses and renormalizes.  std::invalid_argument on a bad
     // qubit, std::runtime_error when the drawn outcome has probability < 1e-15.
@@ -108,5 +123,11 @@ private:
     std::vector<double> uniforms(int count);
     void release();
 };
+
+// Host helpers behind entanglementEntropy (csrc/host/Marginal.cpp): the ascending eigenvalues of a
+// Hermitian dim x dim matrix (row-major) by cyclic Jacobi sweeps, and the entropy in bits of a
+// density matrix as defined above.  std::invalid_argument when the size is not dim x dim.
+std::vector<double> hermitianEigenvalues(std::vector<std::complex<double>> matrix, int dim);
+double hermitianEntropy(const std::vector<std::complex<double>>& rho, int dim, bool renyi2 = false);
 
 }  // namespace qsim

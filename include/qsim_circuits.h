@@ -39,6 +39,12 @@ const char* qsim_circuits_last_error(void);
  * it sets no message in qsim_circuits_last_error(). */
 int qsim_pauli_term_make(int n_qubits, const int32_t* qubits, const char* letters, size_t count,
                          double coeff, qsim_pauli_term* out);
+/* qsim::hermitianEntropy (include/qsim/StateVector.hpp) through the C ABI: the entropy in bits of
+ * the dim x dim density matrix rho (row-major, interleaved re/im, 1 <= dim <= 64), von Neumann from
+ * the host's cyclic Jacobi eigenvalues, or -log2 Tr rho^2 with renyi2 != 0.  Lets a non-C++ host
+ * check the routine behind StateVector::entanglementEntropy; null pointers or a bad dim ->
+ * QSIM_ERR_INVALID_ARGUMENT. */
+int qsim_hermitian_entropy(const double* rho, int dim, int renyi2, double* out);
 
 #ifdef __cplusplus
 }

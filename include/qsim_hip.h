@@ -324,6 +324,38 @@ int qsim_state_expectation(qsim_state* s, const qsim_pauli_term* terms, size_t c
 int qsim_expectation_plan(int n_qubits, const qsim_pauli_term* terms, size_t count, const int32_t* perm,
                           int* passes, int* launches);
 
+/* ---- marginal probabilities and reduced density matrices of a subset of qubits (no reference
+ * counterpart: a caller copies 2^n probabilities to the host and reduces them there) ----
+ * qubits: k distinct LOGICAL qubits in any order, in the convention of the gates and of
+ * qsim_pauli_term: qubit q is index bit q (not the big-endian mapping of the C++ measure(q)).
+ * Bit j of an output index is qubit qubits[j], so the order of the list decides the bit order.
+ * Both readers work like qsim_state_expectation: pending gates of a run-sharing cycle are flushed,
+ * the qubits are mapped through the state's current layout on the host, and ONE streaming read of
+ * the state (16 B per amplitude) is made where it lies; the layout (qsim_state_perm), a relayout
+ * plan's current buffer and the amplitudes are left exactly as they are.  Partial sums are added
+ * in a fixed order (no floating-point atomics): bitwise reproducible.  Both synchronise.
+ * A duplicate qubit, k above the cap (or above n), null out, a null handle, null qubits with
+ * k > 0 -> QSIM_ERR_INVALID_ARGUMENT; a qubit < 0 or >= n -> QSIM_ERR_OUT_OF_RANGE.
+ *
+ * out[m] = sum of |psi_i|^2 over all i whose bit qubits[j] equals bit j of m, m < 2^k;
+ * 0 <= k <= min(n, 20); k == 0: out[0] = the total probability.  Device scratch for partial sums
+ * stays <= 64 MiB for every qubit choice. */
+int qsim_state_marginal_probabilities(qsim_state* s, const int32_t* qubits, int k, double* out);
+/* out = rho_A, 2^k x 2^k row-major, interleaved re/im (2 * 4^k doubles), 0 <= k <= min(n, 6):
+ * rho_A[a][a'] = sum_b psi(a, b) conj(psi(a', b)), a over the listed qubits, b over the others.
+ * The upper triangle is mirrored and the diagonal is real, so rho_A equals its conjugate
+ * transpose bitwise; the diagonal is the marginal.  k == 0: the 1 x 1 matrix holding the norm. */
+int qsim_state_reduced_density_matrix(qsim_state* s, const int32_t* qubits, int k, double* out);
+/* Host-only (no GPU): how the lowering splits the work for these qubits under the layout perm
+ * (logical -> physical, n entries; null: identity); rdm != 0: for the matrix.  info[0] = k_lo,
+ * selected physical positions below the work-group's contiguous run of 2^min(n, 12) amplitudes;
+ * [1] = k_hi, those above; [2] = slices of the unselected high positions (matrix: = [3]);
+ * [3] = work-groups of the first kernel; [4], [5] = scratch bytes of the partial sums, low and high
+ * word; [6] = kernel launches; [7] reserved (0).  The argument checks and error codes of the two
+ * entries above; a perm that is no permutation -> QSIM_ERR_INVALID_ARGUMENT. */
+int qsim_marginal_plan(int n_qubits, const int32_t* qubits, int k, const int32_t* perm, int rdm,
+                       int32_t info[8]);
+
 /* ---- adjoint-method gradients of <psi|H|psi> (no reference counterpart) ----
  * dst = H src out of place, one streaming pass per group of terms sharing an x mask (same qubit
  * count and device; src == dst -> QSIM_ERR_INVALID_ARGUMENT).  dst takes src's qubit layout.

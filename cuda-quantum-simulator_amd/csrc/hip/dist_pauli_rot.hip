@@ -27,11 +27,12 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cstring>
 #include <cmath>
 #include <vector>
 
 #include "device_ops.hpp"
-#include "engine.hpp"
+#include "dist_state.hpp"
 
 namespace qsim_hip {
 
@@ -158,4 +159,237 @@ void launch_dist_pauli_rot(double2* own, const double2* peer, const double2* lam
     if (braket) launch_sum_partials(d_partials, (int)blocks, 1, d_out, false, s);
 }
 
+// The peers' whole shards `src` (one per shard of this process, this rank's own data) into the
+// staging buffers (recv: the receive buffers, else the send buffers) for the pairing r <-> r ^ x_rank,
+// on the comm stream after everything queued on d->stream so far (event 0: src written, the
+// buffer's last readers done); `landed` is recorded when the shards have arrived.
+static void post_peer_shards(qsim_dist* d, const std::vector<double2*>& src, uint64_t x_rank, bool recv,
+                             hipEvent_t landed, const char* what) {
+    QSIM_HIPCHK(hipEventRecord(d->events[0], d->stream));
+    QSIM_HIPCHK(hipStreamWaitEvent(d->comm_stream, d->events[0], 0));
+    std::vector<Post> posts;
+    for (size_t i = 0; i < d->shards.size(); ++i) {
+        const Shard& sh = d->shards[i];
+        posts.push_back({sh.rank, (int)((uint64_t)sh.rank ^ x_rank), src[i], recv ? sh.recvbuf : sh.sendbuf,
+                         1ull << d->L});
+    }
+    post_transfers(d, posts, what);
+    QSIM_HIPCHK(hipEventRecord(landed, d->comm_stream));
+}
+
+// The sequence on the state's shards, in order (qsim_dist_apply_pauli_rotations).  A cross rotation
+// sends each shard itself; its kernel, the shard's next writer, waits for the transfer (event 1),
+// which has then read the shard on this rank and landed the peer's in the receive buffer.
+static void pauli_rotations_dist(qsim_dist* d, const DistPauliRotPlan& plan) {
+    const int L = d->L;
+    const size_t S = d->shards.size();
+    if (plan.cross && d->world == 1) fail(QSIM_ERR_RUNTIME, "cross-rank Pauli rotation in a world of one");
+    if (plan.cross) ensure_events(d, 5);
+    const double sent_before = d->sent_bytes;  // (remapBytes() stays the last run's)
+    // every phase run's table in one upload per shard (sequence order), before the first launch
+    if (plan.phase) {
+        while (d->rot_terms.size() < S) d->rot_terms.emplace_back(new DevBuf());
+        for (size_t i = 0; i < S; ++i) {
+            std::vector<ExpectTerm> tab;
+            tab.reserve(plan.phase);
+            for (const DistPauliRot& r : plan.rots)
+                if (r.cls == DPR_PHASE) tab.push_back(ExpectTerm{r.z_loc, dist_pauli_shard_rot(r, d->shards[i].rank).theta, 0.0});
+            d->rot_terms[i]->upload(tab.data(), tab.size() * sizeof(ExpectTerm), d->stream);
+        }
+    }
+    std::vector<double2*> own(S);
+    for (size_t i = 0; i < S; ++i) own[i] = d->shards[i].d;
+    size_t done = 0;  // phase rotations launched so far
+    for (size_t k = 0; k < plan.rots.size();) {
+        const DistPauliRot& r = plan.rots[k];
+        if (r.cls == DPR_PHASE) {
+            size_t end = k;
+            while (end < plan.rots.size() && plan.rots[end].cls == DPR_PHASE) ++end;
+            for (size_t i = 0; i < S; ++i)
+                launch_pauli_phase(own[i], L, (const ExpectTerm*)d->rot_terms[i]->ptr + done, end - k, d->stream, &d->timer);
+            done += end - k;
+            k = end;
+            continue;
+        }
+        if (r.cls == DPR_LOCAL) {
+            for (size_t i = 0; i < S; ++i)
+                launch_pauli_rot(own[i], L, dist_pauli_shard_rot(r, d->shards[i].rank), d->stream, &d->timer);
+        } else {
+            post_peer_shards(d, own, r.x_rank, true, d->events[1], "Pauli rotation shard send/recv");
+            QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[1], 0));
+            for (size_t i = 0; i < S; ++i)
+                launch_dist_pauli_rot(own[i], d->shards[i].recvbuf, nullptr, L, r, d->shards[i].rank, false, true,
+                                      d->d_partials, nullptr, d->stream, &d->timer);
+        }
+        ++k;
+    }
+    d->sent_bytes = sent_before;
+}
+
+// One step of the rotation sweep (pauli_gradient_dist): slots[i] = shard i's share of
+// Im <lambda| P |phi>, then exp(+i theta/2 P) on both work states; last (the sequence's first
+// rotation): the bra-ket alone.  A cross step receives the peer's old phi shard (receive buffer,
+// event 1), then its old lambda shard (send buffer, event 2): both transfers are queued before
+// the first kernel, so lambda crosses while phi is updated, and each work shard is overwritten
+// only after the transfer that sends it has completed.
+static void pauli_grad_step(qsim_dist* d, qsim_dist::GradWork& w, const DistPauliRot& r, double* slots, bool last) {
+    const int L = d->L;
+    const size_t S = d->shards.size();
+    if (r.cls != DPR_CROSS) {
+        for (size_t i = 0; i < S; ++i) {
+            const int rank = d->shards[i].rank;
+            launch_pauli_adjoint_step(w.phi[i], w.lam[i], L, PauliRot{r.x_loc, r.z_loc, r.theta}, !last, d->d_partials,
+                                      slots + i, d->stream, &d->timer, dist_pauli_rank_neg(r, rank));
+        }
+        return;
+    }
+    if (d->world == 1) fail(QSIM_ERR_RUNTIME, "cross-rank gradient step in a world of one");
+    post_peer_shards(d, w.phi, r.x_rank, true, d->events[1], "Pauli gradient phi shard send/recv");
+    if (!last) {
+        std::vector<Post> posts;
+        for (size_t i = 0; i < S; ++i) {
+            const Shard& sh = d->shards[i];
+            posts.push_back({sh.rank, (int)((uint64_t)sh.rank ^ r.x_rank), w.lam[i], sh.sendbuf, 1ull << L});
+        }
+        post_transfers(d, posts, "Pauli gradient lambda shard send/recv");
+        QSIM_HIPCHK(hipEventRecord(d->events[2], d->comm_stream));
+    }
+    QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[1], 0));
+    for (size_t i = 0; i < S; ++i)
+        launch_dist_pauli_rot(w.phi[i], d->shards[i].recvbuf, w.lam[i], L, r, d->shards[i].rank, true, !last,
+                              d->d_partials, slots + i, d->stream, &d->timer);
+    if (last) return;
+    QSIM_HIPCHK(hipStreamWaitEvent(d->stream, d->events[2], 0));
+    for (size_t i = 0; i < S; ++i)
+        launch_dist_pauli_rot(w.lam[i], d->shards[i].sendbuf, nullptr, L, r, d->shards[i].rank, true, true,
+                              d->d_partials, nullptr, d->stream, &d->timer);
+}
+
+// The value and the sweep of qsim_dist_pauli_gradient, on the state the sequence left.  Rotations
+// never change the map: no segments, no remaps, the work map stays the state's.
+static void pauli_gradient_dist(qsim_dist* d, const DistPauliRotPlan& plan, const qsim_pauli_term* terms,
+                                size_t nterms, double* value, double* grad) {
+    const size_t S = d->shards.size(), P = plan.rots.size();
+    *value = 0.0;
+    for (size_t k = 0; k < P; ++k) grad[k] = 0.0;
+    const DistApplyPlan ap = lower_dist_apply(d->n, d->L, terms, nterms, d->perm.data());
+    if (ap.all.terms.empty()) {  // H = 0 (no terms, or every coefficient cancels): no sweep
+        stream_wait(d, d->stream);
+        return;
+    }
+    // (the work shards first: a failed allocation leaves nothing queued)
+    qsim_dist::GradWork* wp = P ? &ensure_grad(d, P) : nullptr;
+    *value = expectation_dist(d, terms, nterms);
+    if (!wp) return;
+    qsim_dist::GradWork& w = *wp;
+    const double sent_before = d->sent_bytes;  // (remapBytes() stays the last run's)
+    grad_load_work(d, w, ap);
+    // the sweep: slot [rotation k][shard i], every rotation its own step, last to first
+    QSIM_HIPCHK(hipMemsetAsync(w.d_slots, 0, P * (S + 1) * sizeof(double), d->stream));
+    for (size_t k = P; k-- > 0;) pauli_grad_step(d, w, plan.rots[k], w.d_slots + k * S, k == 0);
+    grad_reduce(d, w, P, grad);
+    d->sent_bytes = sent_before;
+}
+
+// Host-only mirror of pauli_rotations_dist (qsim_dist_pauli_rotation_plan).
+static void pauli_rotation_info(const DistPauliRotPlan& plan, int L, qsim_dist_pauli_rotation_info* out) {
+    std::memset(out, 0, sizeof(*out));
+    out->rotations = (int32_t)plan.rots.size();
+    out->phase_rotations = (int32_t)plan.phase;
+    out->phase_passes = (int32_t)plan.phase_passes;
+    out->local_rotations = (int32_t)plan.local;
+    out->cross_rotations = (int32_t)plan.cross;
+    out->cross_pure = (int32_t)plan.cross_pure;
+    out->launches = (int32_t)plan.launches;
+    out->transfers = (int32_t)plan.cross;
+    out->bytes_sent_per_rank = (uint64_t)plan.cross * ((uint64_t)sizeof(double2) << L);
+}
+
 }  // namespace qsim_hip
+
+using namespace qsim_hip;
+
+extern "C" {
+
+int qsim_dist_apply_pauli_rotations(qsim_dist* d, const qsim_pauli_term* rots, size_t count) {
+    return dguard_comm(d, [&] {
+        need(d);
+        if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        if (count == 0) return;
+        // (the lowering checks every mask of the sequence: nothing is launched or posted before)
+        const DistPauliRotPlan plan = lower_dist_pauli_rotations(d->n, d->L, rots, count, d->perm.data());
+        QSIM_HIPCHK(hipSetDevice(d->device));
+        flush_carry(d);  // (the previous run's last step, if it was left pending)
+        d->fresh = false;
+        pauli_rotations_dist(d, plan);
+    });
+}
+
+int qsim_dist_pauli_rotation_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* rots,
+                                  size_t count, qsim_dist_pauli_rotation_info* out) {
+    return dguard([&] {
+        if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
+        const int L = HostPlanArgs(n_qubits, world).L;
+        if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        const std::vector<int> p = checked_perm(n_qubits, perm);
+        pauli_rotation_info(lower_dist_pauli_rotations(n_qubits, L, rots, count, p.data()), L, out);
+    });
+}
+
+int qsim_dist_pauli_gradient(qsim_dist* d, const qsim_pauli_term* rots, size_t count, const qsim_pauli_term* terms,
+                             size_t nterms, double* value, double* grad) {
+    int rc = dguard([&] {
+        need(d);
+        if (!value) fail(QSIM_ERR_INVALID_ARGUMENT, "null value");
+        if (!grad && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gradient");
+        if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        if (!terms && nterms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        // (the observable before the sequence is applied; the sequence's masks: by that call)
+        check_pauli_masks(d->n, terms, nterms, "Pauli term");
+    });
+    if (rc != QSIM_OK) return rc;
+    // The forward pass is qsim_dist_apply_pauli_rotations itself: the state ends exactly as that
+    // call alone leaves it, and nothing below writes to it.
+    if ((rc = qsim_dist_apply_pauli_rotations(d, rots, count)) != QSIM_OK) return rc;
+    return dguard_comm(d, [&] {
+        QSIM_HIPCHK(hipSetDevice(d->device));
+        flush_carry(d);  // (count == 0: nothing above has flushed)
+        const DistPauliRotPlan plan = lower_dist_pauli_rotations(d->n, d->L, rots, count, d->perm.data());
+        pauli_gradient_dist(d, plan, terms, nterms, value, grad);
+    });
+}
+
+int qsim_dist_pauli_gradient_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* rots,
+                                  size_t count, const qsim_pauli_term* terms, size_t nterms,
+                                  qsim_dist_pauli_gradient_info* out) {
+    return dguard([&] {
+        if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
+        const int L = HostPlanArgs(n_qubits, world).L;
+        if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        if (!terms && nterms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        check_pauli_masks(n_qubits, terms, nterms, "Pauli term");
+        const std::vector<int> p = checked_perm(n_qubits, perm);
+        const DistPauliRotPlan plan = lower_dist_pauli_rotations(n_qubits, L, rots, count, p.data());
+        const DistApplyPlan ap = lower_dist_apply(n_qubits, L, terms, nterms, p.data());
+        std::memset(out, 0, sizeof(*out));
+        pauli_rotation_info(plan, L, &out->forward);
+        out->first_class = -1;
+        out->bytes_sent_per_rank = out->forward.bytes_sent_per_rank;
+        if (ap.all.terms.empty() || plan.rots.empty()) return;  // no sweep
+        out->apply_groups_local = (int32_t)ap.local_groups;
+        out->apply_groups_cross = (int32_t)ap.cross_groups;
+        out->apply_transfers = (int32_t)ap.transfers;
+        out->apply_launches = (int32_t)ap.launches;
+        out->steps = (int32_t)plan.rots.size();
+        out->steps_phase = (int32_t)plan.phase;
+        out->steps_local = (int32_t)plan.local;
+        out->steps_cross = (int32_t)plan.cross;
+        out->first_class = plan.rots.front().cls;
+        // (phi and lambda per cross step; the sequence's first rotation needs phi alone)
+        out->step_transfers = (int32_t)(2 * plan.cross) - (plan.rots.front().cls == DPR_CROSS ? 1 : 0);
+        out->bytes_sent_per_rank +=
+            (uint64_t)(out->apply_transfers + out->step_transfers) * ((uint64_t)sizeof(double2) << L);
+    });
+}
+
+}  // extern "C"

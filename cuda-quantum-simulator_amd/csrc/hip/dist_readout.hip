@@ -14,11 +14,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "device_ops.hpp"
-#include "engine.hpp"
-#include "qsim_hip.h"
+#include "dist_state.hpp"
 
 namespace qsim_hip {
 
@@ -229,4 +231,276 @@ void launch_dist_chunk_search(const double2* st, const ChunkMap& m, const ShotJo
     QSIM_HIPCHK(hipGetLastError());
 }
 
+// Physical (rank-major) amplitudes -> logical index order (dst: 2 * 2^n doubles).  The map
+// i -> p(i) moves bit q to perm[q], so p is the OR of per-11-bit-chunk tables; threads split i.
+template <typename Put>
+void unpermute_each(const qsim_dist* d, Put&& put) {
+    const int n = d->n, nch = (n + 10) / 11;
+    std::vector<uint64_t> tab((size_t)nch << 11, 0);
+    for (int c = 0; c < nch; ++c)
+        for (uint64_t v = 0; v < 2048; ++v)
+            for (int b = 0; b < 11 && c * 11 + b < n; ++b)
+                if ((v >> b) & 1ull) tab[((size_t)c << 11) + v] |= 1ull << d->perm[c * 11 + b];
+    const uint64_t N = 1ull << n;
+    const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(16, N >> 16));
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < T; ++t)
+        th.emplace_back([&, t] {
+            for (uint64_t i = N * t / T; i < N * (t + 1) / T; ++i) {
+                uint64_t p = 0;
+                for (int c = 0; c < nch; ++c) p |= tab[((size_t)c << 11) + ((i >> (11 * c)) & 2047)];
+                put(i, p);
+            }
+        });
+    for (auto& x : th) x.join();
+}
+void unpermute(const qsim_dist* d, const std::vector<double2>& phys, double* dst) {
+    unpermute_each(d, [&](uint64_t i, uint64_t p) {
+        dst[2 * i] = phys[p].x;
+        dst[2 * i + 1] = phys[p].y;
+    });
+}
+
+static double prob_bit_zero(qsim_dist* d, int q) {
+    const int p = d->perm[q];
+    double local = 0.0;
+    for (const Shard& s : d->shards) {
+        if (p < d->L) local += reduce_norm(s.d, d->L, p, d->d_partials, d->d_result, d->stream);
+        else if (!((s.rank >> (p - d->L)) & 1))
+            local += reduce_norm(s.d, d->L, -1, d->d_partials, d->d_result, d->stream);
+    }
+    return allreduce_sum(d, local);
+}
+
+// Zero the amplitudes whose logical bit q != result, scale the rest; the layout stays.
+static void collapse_bit(qsim_dist* d, int q, int result, double scale) {
+    const int p = d->perm[q];
+    for (const Shard& s : d->shards) {
+        if (p < d->L) {
+            launch_collapse(s.d, d->L, p, result, scale, d->stream);
+            continue;
+        }
+        // the whole shard shares the bit: k_collapse on a bit above the shard reads 0 everywhere,
+        // so result 0 scales every amplitude and result 1 zeroes every amplitude
+        const int mine = (s.rank >> (p - d->L)) & 1;
+        launch_collapse(s.d, d->L, 63, mine == result ? 0 : 1, scale, d->stream);
+    }
+    stream_wait(d, d->stream);
+}
+
+// Bring logical qubits 0 .. c-1 to local positions with one remap: each one on a rank position
+// trades places with a logical qubit >= c on the highest local positions (long pack runs).  Pure
+// copies (pack, transfer, unpack): amplitudes keep their bits, only the map changes.
+static void localize_low(qsim_dist* d, int c) {
+    std::vector<int> out;
+    for (int q = 0; q < c; ++q)
+        if (d->perm[q] >= d->L) out.push_back(q);
+    if (out.empty()) return;
+    std::vector<int> inv(d->n);
+    for (int q = 0; q < d->n; ++q) inv[d->perm[q]] = q;
+    std::vector<int> in;
+    for (int p = d->L - 1; p >= 0 && in.size() < out.size(); --p)
+        if (inv[p] >= c) in.push_back(inv[p]);
+    if (in.size() != out.size() || out.size() > 8) fail(QSIM_ERR_RUNTIME, "sampler: no remap localizes the chunk qubits");
+    DStep ex;
+    ex.kind = 1;
+    ex.k = (int)out.size();
+    for (int j = 0; j < ex.k; ++j) {
+        ex.gpos[j] = d->perm[out[j]];
+        ex.lpos[j] = d->perm[in[j]];
+    }
+    exchange(d, ex, std::vector<char>(d->shards.size(), 0));
+    for (int j = 0; j < ex.k; ++j) {
+        d->perm[out[j]] = ex.lpos[j];
+        d->perm[in[j]] = ex.gpos[j];
+    }
+    stream_wait(d, d->stream);
+}
+
+// The sampler (qsim_dist_sample; see the top of this file).  Every rank computes the same chunk
+// totals (all-reduced), hence the same chunk and target per shot; a shot's chunk is searched by
+// the rank that owns it, and the indices are combined by a second all-reduce.
+static void sample_dist(qsim_dist* d, const double* uniforms, int shots, int64_t* out) {
+    const int n = d->n, L = d->L, c = dist_chunk_log(L);
+    localize_low(d, c);
+    const uint64_t nchunks = 1ull << (n - c);
+    std::vector<ChunkMap> maps;
+    size_t npart = 0;
+    for (const Shard& sh : d->shards) {
+        maps.push_back(make_chunk_map(n, L, c, sh.rank, d->perm.data()));
+        npart = std::max(npart, dist_chunk_partials_count(maps.back()));
+    }
+    // scratch = [chunk sums][partials][jobs][index of shot (double)]
+    const size_t b_sums = nchunks * sizeof(double), b_part = npart * sizeof(double);
+    const size_t b_jobs = (size_t)shots * sizeof(ShotJob), b_out = (size_t)shots * sizeof(double);
+    char* base = (char*)d->readout.get(b_sums + b_part + b_jobs + b_out, d->stream);
+    double* d_sums = (double*)base;
+    double* d_part = (double*)(base + b_sums);
+    ShotJob* d_jobs = (ShotJob*)(base + b_sums + b_part);
+    double* d_out = (double*)(base + b_sums + b_part + b_jobs);
+    QSIM_HIPCHK(hipMemsetAsync(d_sums, 0, b_sums, d->stream));
+    for (size_t i = 0; i < d->shards.size(); ++i) {
+        TimedLaunch tl(&d->timer, "dist_chunk_sums", 16.0 * (double)(1ull << L), d->stream);
+        launch_dist_chunk_sums(d->shards[i].d, maps[i], nchunks, d_part, d_sums, d->stream);
+    }
+    std::vector<double> sums(nchunks);
+    allreduce_vec(d, d_sums, nchunks, sums.data());
+    std::vector<int64_t> chunk_of(shots);
+    std::vector<double> target(shots);
+    chunk_targets(sums.data(), nchunks, uniforms, shots, chunk_of.data(), target.data());
+    // jobs grouped by owning shard (shard order), one upload
+    std::vector<std::vector<ShotJob>> per(d->shards.size());
+    for (int s = 0; s < shots; ++s) {
+        if (chunk_of[s] < 0) continue;
+        uint64_t phys = 0;
+        for (int b = 0; b < n - c; ++b)
+            if (((uint64_t)chunk_of[s] >> b) & 1ull) phys |= 1ull << d->perm[c + b];
+        const int owner = (int)(phys >> L);
+        for (size_t i = 0; i < d->shards.size(); ++i)
+            if (d->shards[i].rank == owner)
+                per[i].push_back({phys & ((1ull << L) - 1ull), (uint64_t)chunk_of[s] << c, target[s], (int64_t)s});
+    }
+    std::vector<ShotJob> jobs;
+    for (const auto& v : per) jobs.insert(jobs.end(), v.begin(), v.end());
+    if (!jobs.empty())
+        QSIM_HIPCHK(hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(ShotJob), hipMemcpyHostToDevice, d->stream));
+    QSIM_HIPCHK(hipMemsetAsync(d_out, 0, b_out, d->stream));
+    size_t at = 0;
+    for (size_t i = 0; i < d->shards.size(); ++i) {
+        TimedLaunch tl(&d->timer, "dist_chunk_search", 0.0, d->stream);
+        launch_dist_chunk_search(d->shards[i].d, maps[i], d_jobs + at, (int)per[i].size(), shots, d_out, d->stream);
+        at += per[i].size();
+    }
+    std::vector<double> idx(shots);
+    allreduce_vec(d, d_out, (size_t)shots, idx.data());
+    for (int s = 0; s < shots; ++s) out[s] = chunk_of[s] < 0 ? (int64_t)(1ull << n) : (int64_t)idx[s];
+}
+
 }  // namespace qsim_hip
+
+using namespace qsim_hip;
+
+extern "C" {
+
+int qsim_dist_total_probability(qsim_dist* d, double* out) {
+    return dguard_comm(d, [&] {
+        need(d);
+        flush_on_device(d);
+        double local = 0.0;
+        for (const Shard& s : d->shards)
+            local += reduce_norm(s.d, d->L, -1, d->d_partials, d->d_result, d->stream);
+        *out = allreduce_sum(d, local);
+    });
+}
+
+int qsim_dist_prob_bit_zero(qsim_dist* d, int q, double* out) {
+    return dguard_comm(d, [&] {
+        need(d);
+        QSIM_HIPCHK(hipSetDevice(d->device));
+        flush_carry(d);  // (the previous run's last step, if it was left pending)
+        if (q < 0 || q >= d->n) fail(QSIM_ERR_INVALID_ARGUMENT, "bit out of range");
+        QSIM_HIPCHK(hipSetDevice(d->device));
+        *out = prob_bit_zero(d, q);
+    });
+}
+
+int qsim_dist_probabilities(qsim_dist* d, double* dst) {
+    return dguard_comm(d, [&] {
+        need(d);
+        flush_on_device(d);
+        const uint64_t shard = 1ull << d->L;
+        const bool root = d->virt || d->shards[0].rank == 0;
+        // |a|^2 per shard on the device, then the gather of qsim_dist_gather_state at 8 B per
+        // amplitude: rank 0 collects the shards in rank order (physical order) and un-permutes
+        const bool staged = root && !d->virt && d->transport != qsim_dist::T_HOSTED && d->world > 1;
+        double* dp = (double*)d->readout.get(sizeof(double) * (staged ? (shard << d->g) : shard), d->stream);
+        std::vector<double> phys(root ? (1ull << d->n) : shard);
+        if (d->virt) {
+            for (const Shard& s : d->shards) {
+                launch_probabilities(s.d, shard, dp, d->stream);
+                QSIM_HIPCHK(hipMemcpyAsync(phys.data() + s.rank * shard, dp, sizeof(double) * shard,
+                                           hipMemcpyDeviceToHost, d->stream));
+            }
+            stream_wait(d, d->stream);
+        } else if (d->transport == qsim_dist::T_HOSTED) {
+            launch_probabilities(d->shards[0].d, shard, dp, d->stream);
+            QSIM_HIPCHK(hipMemcpyAsync(phys.data(), dp, sizeof(double) * shard, hipMemcpyDeviceToHost, d->stream));
+            QSIM_HIPCHK(hipStreamSynchronize(d->stream));
+            std::vector<qsim_dist_post> hp;
+            if (root)
+                for (int r = 1; r < d->world; ++r)
+                    hp.push_back({r, 0, sizeof(double) * shard, nullptr, phys.data() + r * shard});
+            else
+                hp.push_back({0, 0, sizeof(double) * shard, phys.data(), nullptr});
+            if (!hp.empty()) host_call(d, hp, "gather of probabilities");
+        } else {
+            launch_probabilities(d->shards[0].d, shard, dp, d->stream);
+            if (d->world > 1) {
+                QSIM_NCCLCHK(ncclGroupStart());
+                if (root)
+                    for (int r = 1; r < d->world; ++r)
+                        QSIM_NCCLCHK(ncclRecv(dp + r * shard, shard, ncclDouble, r, d->comm, d->stream));
+                else
+                    QSIM_NCCLCHK(ncclSend(dp, shard, ncclDouble, 0, d->comm, d->stream));
+                QSIM_NCCLCHK(ncclGroupEnd());
+                comm_settle(d, "gather of probabilities");
+            }
+            if (root)
+                QSIM_HIPCHK(hipMemcpyAsync(phys.data(), dp, sizeof(double) << d->n, hipMemcpyDeviceToHost, d->stream));
+            stream_wait(d, d->stream);
+        }
+        if (root && dst) unpermute_each(d, [&](uint64_t i, uint64_t p) { dst[i] = phys[p]; });
+    });
+}
+
+int qsim_dist_sample(qsim_dist* d, const double* uniforms, int shots, int64_t* out) {
+    return dguard_comm(d, [&] {
+        need(d);
+        if (shots <= 0) return;
+        if (!uniforms || !out) fail(QSIM_ERR_INVALID_ARGUMENT, "null buffer");
+        flush_on_device(d);
+        sample_dist(d, uniforms, shots, out);
+    });
+}
+
+int qsim_dist_collapse(qsim_dist* d, int logical_bit, int result, double scale) {
+    return dguard_comm(d, [&] {
+        need(d);
+        if (logical_bit < 0 || logical_bit >= d->n) fail(QSIM_ERR_INVALID_ARGUMENT, "bit out of range");
+        if (result != 0 && result != 1) fail(QSIM_ERR_INVALID_ARGUMENT, "result must be 0 or 1");
+        flush_on_device(d);
+        d->fresh = false;
+        collapse_bit(d, logical_bit, result, scale);
+    });
+}
+
+int qsim_dist_measure(qsim_dist* d, int logical_bit, double u, int* result) {
+    return dguard_comm(d, [&] {
+        need(d);
+        if (!result) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (logical_bit < 0 || logical_bit >= d->n) fail(QSIM_ERR_INVALID_ARGUMENT, "bit out of range");
+        flush_on_device(d);
+        // p0 is all-reduced (the same on every rank) and u is the same by contract: every rank
+        // decides alike
+        const double p0 = prob_bit_zero(d, logical_bit);
+        const int r = u < p0 ? 0 : 1;
+        const double pr = r == 0 ? p0 : 1.0 - p0;
+        if (pr < 1e-15)
+            fail(QSIM_ERR_RUNTIME, "Measurement result " + std::to_string(r) + " has zero probability");
+        d->fresh = false;
+        collapse_bit(d, logical_bit, r, 1.0 / std::sqrt(pr));
+        *result = r;
+    });
+}
+
+int qsim_dist_sample_plan(int n_qubits, int world, const int32_t* perm, int* chunk_log, uint64_t* localize_mask) {
+    return dguard([&] {
+        const int L = HostPlanArgs(n_qubits, world).L, c = dist_chunk_log(L);
+        if (!perm) fail(QSIM_ERR_INVALID_ARGUMENT, "null qubit map");
+        const std::vector<int> p = checked_perm(n_qubits, perm);
+        if (chunk_log) *chunk_log = c;
+        if (localize_mask) *localize_mask = dist_localize_mask(n_qubits, L, c, p.data());
+    });
+}
+
+}  // extern "C"

@@ -504,7 +504,7 @@ void chunk_targets(const double* sums, uint64_t nchunks, const double* uniforms,
                    int64_t* chunk_of, double* target);
 void sample_indices(const double2* st, int n, uint64_t batch, const double* uniforms, int shots,
                     int64_t* out, hipStream_t s, Scratch& scratch);
-// ---- readout of a sharded state (dist_readout.hip; the collectives around it: dist.hip) ----
+// ---- readout of a sharded state (dist_readout.hip; the collectives it uses: dist_exchange.hip) ----
 // A chunk: the 2^c amplitudes sharing all logical index bits >= c, c = min(kDistChunkLog, L).
 constexpr int kDistChunkLog = 12;
 int dist_chunk_log(int L);
@@ -648,7 +648,7 @@ void launch_dm_expectation(const double2* rho, const DmExpectPlan& plan, DevBuf&
                            double* d_out, hipStream_t s, Timer* tm);
 
 // Pauli-sum expectation values on a sharded state (lowering: dist_expect.hip; the launch: expect.hip;
-// the transfers and collectives around it: dist.hip).  A physical x mask splits into local bits (< L) and rank bits:
+// the transfers and collectives it uses: dist_exchange.hip).  A physical x mask splits into local bits (< L) and rank bits:
 // x = x_loc | x_rank << L.  Groups with x_rank == 0 pair inside a shard (launch_expectation on the
 // shard, n = L); a group with x_rank != 0 pairs shard r with shard r ^ x_rank and needs half of
 // the peer's shard.  Cross groups with the same key (x_rank, top local position in x_loc) share
@@ -752,7 +752,7 @@ void launch_pauli_adjoint_step(double2* phi, double2* lam, int n, const PauliRot
                                double* d_out, hipStream_t s, Timer* tm, bool negate = false);
 
 // Pauli-string rotations on a sharded state (dist_pauli_rot.hip; the transfers and collectives
-// around them: dist.hip).  A rotation's physical masks split as x = x_loc | x_rank << L, z alike.
+// they use: dist_exchange.hip).  A rotation's physical masks split as x = x_loc | x_rank << L, z alike.
 enum {
     DPR_PHASE = 0,  // x == 0: part of a run of Z/I-only rotations, pauli_phase on each shard
     DPR_LOCAL = 1,  // x_rank == 0, x_loc != 0: pauli_rot on each shard
@@ -790,7 +790,7 @@ void launch_dist_pauli_rot(double2* own, const double2* peer, const double2* lam
                            Timer* tm);
 
 // Adjoint-method gradients on a sharded state (dist_adjoint.hip; the transfers, the inverted
-// segments and the collectives around it: dist.hip).
+// segments and the collectives it uses: dist_plan.hip, dist_run.hip, dist_exchange.hip).
 // lambda = H phi on shards: lower_pauli_apply over the n physical positions, each group's x mask
 // split into x_loc | x_rank << L.  Groups come ordered by x, so groups of one x_rank are adjacent
 // and share the transfer of the peer's phi shard.

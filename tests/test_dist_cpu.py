@@ -144,7 +144,7 @@ def test_plan_pivots_rank_independent_fresh(qsim, n, seed):
     import qsim_amd.dist as qd
     world = 8
     # (these circuits made ranks != 0 pick other pivots when the planner read the roles of
-    # rank 0's reference plan instead of its own marks — ADVICE r2, dist.hip mark_overlap)
+    # rank 0's reference plan instead of its own marks — ADVICE r2, dist_plan.hip mark_overlap)
     c = qsim.createRandomHCCircuit(n, 300, seed)
     ref = None
     for r in range(world):

@@ -1,5 +1,5 @@
 """GPU: adjoint-method gradients on the sharded state (DistributedSimulator.gradient,
-qsim_dist_gradient; csrc/hip/dist_adjoint.hip and the driver in dist.hip) on virtual ranks.
+qsim_dist_gradient; csrc/hip/dist_adjoint.hip, kernels and driver) on virtual ranks.
 
 Reference: tests/gradient_cases.py (dense numpy adjoint sweep) on the simulator's own amplitudes
 read before the call, and Simulator.gradient on the same inputs; bar gc.bound(terms) = 1e-12 *

@@ -1,6 +1,6 @@
 """GPU: Pauli-string rotations, Trotter evolution and their adjoint gradients on the sharded state
 (DistributedSimulator.applyPauliRotation(s) / evolve / pauliGradient; qsim_dist_apply_pauli_rotations,
-qsim_dist_pauli_gradient; csrc/hip/dist_pauli_rot.hip and the driver in dist.hip) on virtual ranks.
+qsim_dist_pauli_gradient; csrc/hip/dist_pauli_rot.hip, kernels and driver) on virtual ranks.
 
 References: tests/pauli_rotation_cases.py and tests/gradient_cases.py (dense numpy) on the simulator's
 own amplitudes read before the call, and the single-GPU Simulator on the same inputs.  Bars: 1e-12

@@ -105,6 +105,32 @@ double DistributedSimulator::expectation(const PauliSum& observable) const {
     return e;
 }
 
+std::vector<double> DistributedSimulator::marginalProbabilities(const std::vector<int>& qubits) const {
+    if (qubits.size() > 20) throw std::invalid_argument("at most 20 qubits in a marginal");
+    std::vector<double> out(size_t(1) << qubits.size());
+    check(qsim_dist_marginal_probabilities(h_, qubits.data(), (int)qubits.size(), out.data()));
+    return out;
+}
+
+std::vector<std::complex<double>> DistributedSimulator::reducedDensityMatrix(const std::vector<int>& qubits) const {
+    if (qubits.size() > 6) throw std::invalid_argument("at most 6 qubits in a reduced density matrix");
+    std::vector<std::complex<double>> out(size_t(1) << (2 * qubits.size()));
+    // std::complex<double> is layout-compatible with double[2] ([complex.numbers.general]).
+    check(qsim_dist_reduced_density_matrix(h_, qubits.data(), (int)qubits.size(),
+                                           reinterpret_cast<double*>(out.data())));
+    return out;
+}
+
+double DistributedSimulator::subsystemPurity(const std::vector<int>& qubits) const {
+    double tr2 = 0.0;
+    for (const auto& v : reducedDensityMatrix(qubits)) tr2 += std::norm(v);
+    return tr2;
+}
+
+double DistributedSimulator::entanglementEntropy(const std::vector<int>& qubits, bool renyi2) const {
+    return hermitianEntropy(reducedDensityMatrix(qubits), 1 << qubits.size(), renyi2);
+}
+
 Gradient DistributedSimulator::gradient(const Circuit& circuit, const PauliSum& observable, RunMode mode) {
     if (circuit.getNumQubits() != num_qubits_)
         throw std::invalid_argument("Circuit qubit count doesn't match simulator");

@@ -260,6 +260,10 @@ _sig(hip, "qsim_dist_expectation", [_P, POINTER(qsim_pauli_term), c_size_t, POIN
 _sig(hip, "qsim_dist_expectation_plan", [c_int, c_int, POINTER(c_int32), POINTER(qsim_pauli_term), c_size_t,
                                          POINTER(c_int), POINTER(c_int), POINTER(c_int), POINTER(c_int),
                                          POINTER(c_uint64)])
+_sig(hip, "qsim_dist_marginal_probabilities", [_P, POINTER(c_int32), c_int, _P])
+_sig(hip, "qsim_dist_reduced_density_matrix", [_P, POINTER(c_int32), c_int, _P])
+_sig(hip, "qsim_dist_marginal_plan", [c_int, c_int, POINTER(c_int32), POINTER(c_int32), c_int, c_int,
+                                      POINTER(c_int32)])
 class qsim_dist_gradient_info(Structure):
     _fields_ = [(k, c_int32) for k in (
         "params", "steps_local", "steps_local_crank", "steps_diag", "steps_diag_crank", "steps_cross",

@@ -198,6 +198,48 @@ class DistributedSimulator:
         _lib.check(_lib.hip.qsim_dist_expectation(self._h, terms, count, _c.byref(e)))
         return e.value
 
+    # -- readout of a subset of qubits where the shards lie (collective; StateVector's conventions:
+    #    qubit q is index bit q, bit j of an output index is qubits[j]; ValueError on a duplicate
+    #    or too many qubits, IndexError on a bad qubit).  The same floats on every rank.
+    def _qubit_list(self, qubits, cap: int):
+        qs = [int(q) for q in qubits]
+        if len(qs) > cap:
+            raise ValueError(f"at most {cap} qubits")
+        return (_c.c_int32 * len(qs))(*qs) if qs else None, len(qs)
+
+    def marginalProbabilities(self, qubits) -> np.ndarray:
+        """The 2^k marginal probabilities of k <= 20 distinct qubits (k = 0: the total probability)
+        of the sharded state (qsim_dist_marginal_probabilities): every shard bins its local
+        positions and one all-reduce of 2^k doubles adds the ranks — no gather, no remap, perm()
+        unchanged, bitwise reproducible."""
+        arr, k = self._qubit_list(qubits, 20)
+        out = np.empty(1 << k, dtype=np.float64)
+        _lib.check(_lib.hip.qsim_dist_marginal_probabilities(self._h, arr, k,
+                                                             out.ctypes.data_as(_c.c_void_p)))
+        return out
+
+    def reducedDensityMatrix(self, qubits) -> np.ndarray:
+        """rho_A of k <= 6 qubits as a 2^k x 2^k complex128 array, bitwise equal to its conjugate
+        transpose (qsim_dist_reduced_density_matrix).  A selected qubit that sits on a rank
+        position pairs ranks: each of the 2^k_rank - 1 steps moves half a shard each way (a whole
+        one when the top local position is selected too)."""
+        arr, k = self._qubit_list(qubits, 6)
+        out = np.empty((1 << k, 1 << k), dtype=np.complex128)
+        _lib.check(_lib.hip.qsim_dist_reduced_density_matrix(self._h, arr, k,
+                                                             out.ctypes.data_as(_c.c_void_p)))
+        return out
+
+    def subsystemPurity(self, qubits) -> float:
+        """Tr rho_A^2 of the k <= 6 qubits."""
+        rho = self.reducedDensityMatrix(qubits)
+        return float(np.sum(rho.real ** 2 + rho.imag ** 2))
+
+    def entanglementEntropy(self, qubits, renyi2: bool = False) -> float:
+        """Von Neumann entropy of rho_A in bits (the host Jacobi routine plan.hermitian_entropy;
+        eigenvalues below 1e-300 contribute 0); renyi2: -log2 Tr rho_A^2 instead."""
+        from .plan import hermitian_entropy
+        return hermitian_entropy(self.reducedDensityMatrix(qubits), renyi2)
+
     def gradient(self, circuit: Circuit, observable, fused: bool = True):
         """(value, gradient) on the sharded state (collective, qsim_dist_gradient): runs `circuit`
         as run() would, then <psi|H|psi> and its derivative with respect to the angle of every
@@ -391,6 +433,29 @@ def expectation_plan(n: int, world: int, perm: Optional[List[int]], observable) 
                                                    _c.byref(tr), _c.byref(la), _c.byref(by)))
     return {"local_groups": lg.value, "cross_groups": cg.value, "transfers": tr.value,
             "launches": la.value, "bytes_sent_per_rank": by.value}
+
+
+def marginal_plan(n: int, world: int, perm: Optional[List[int]], qubits, rdm: bool = False) -> dict:
+    """Host-only (qsim_dist_marginal_plan): what DistributedSimulator.marginalProbabilities (rdm:
+    reducedDensityMatrix) does for these qubits under qubit map `perm` (None: the identity):
+    k_loc / k_rank selected local / rank positions; k_lo, k_hi, slices, work_groups of a shard's
+    own plan (plan.marginal_plan at n = L); cross_steps, transfers and bytes_sent_per_rank;
+    launches per shard (at most), allreduce_doubles, scratch_bytes of the partial sums, pair_rule
+    (0 none, 1 half a shard each way, 2 a whole shard and the lower rank computes) and
+    cross_work_groups.  The readers' argument checks."""
+    if perm is not None and len(perm) != n:
+        raise ValueError("perm needs one entry per qubit")
+    qs = [int(q) for q in qubits]
+    arr = (_c.c_int32 * len(qs))(*qs) if qs else None
+    p = (_c.c_int32 * n)(*perm) if perm is not None else None
+    info = (_c.c_int32 * 16)()
+    _lib.check(_lib.hip.qsim_dist_marginal_plan(n, world, p, arr, len(qs), 1 if rdm else 0, info))
+    return {"k_loc": info[0], "k_rank": info[1], "k_lo": info[2], "k_hi": info[3], "slices": info[4],
+            "work_groups": info[5], "cross_steps": info[6], "transfers": info[7],
+            "bytes_sent_per_rank": (info[8] & 0xffffffff) | (info[9] << 32), "launches": info[10],
+            "allreduce_doubles": info[11],
+            "scratch_bytes": (info[12] & 0xffffffff) | (info[13] << 32), "pair_rule": info[14],
+            "cross_work_groups": info[15]}
 
 
 def gradient_plan(circuit: Circuit, world: int, observable, perm: Optional[List[int]] = None) -> dict:

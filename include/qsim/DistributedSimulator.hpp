@@ -54,6 +54,19 @@ public:
     // (qsim_dist_expectation).  std::invalid_argument on a qubit-count mismatch.
     double expectation(const PauliSum& observable) const;
 
+    // StateVector's readout of a subset of qubits on the sharded state, the same values on every
+    // rank (qsim_dist_marginal_probabilities / qsim_dist_reduced_density_matrix): every shard is
+    // read where it lies, nothing is gathered and no qubit moves; a matrix over qubits that sit
+    // on rank positions pairs ranks and moves at most a shard each way per pair step.
+    // StateVector's conventions (qubit q == index bit q, bit j of an output index is qubits[j]),
+    // caps (20 / 6 qubits) and exceptions: std::invalid_argument on a duplicate or too many
+    // qubits, std::out_of_range on a bad qubit.  Purity and entropy as StateVector's (the entropy
+    // through hermitianEntropy's Jacobi sweep).
+    std::vector<double> marginalProbabilities(const std::vector<int>& qubits) const;
+    std::vector<std::complex<double>> reducedDensityMatrix(const std::vector<int>& qubits) const;
+    double subsystemPurity(const std::vector<int>& qubits) const;
+    double entanglementEntropy(const std::vector<int>& qubits, bool renyi2 = false) const;
+
     // Simulator::gradient on the sharded state (collective, qsim_dist_gradient): runs `circuit` as
     // run() would in `mode`, then <psi|H|psi> and its derivative with respect to the angle of every
     // gate by one backward sweep over two sharded work states; a rotation whose target sits on a

@@ -712,6 +712,45 @@ int qsim_dist_expectation(qsim_dist* d, const qsim_pauli_term* terms, size_t cou
 int qsim_dist_expectation_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* terms,
                                size_t count, int* local_groups, int* cross_groups, int* transfers, int* launches,
                                uint64_t* bytes_sent_per_rank);
+/* qsim_state_marginal_probabilities / qsim_state_reduced_density_matrix on the sharded state
+ * (collective): their conventions, caps (k <= min(n, 20) / k <= min(n, 6)), argument checks and
+ * error codes, all checked on the host before any launch or transfer; the same doubles on EVERY
+ * rank.  Like qsim_dist_expectation they flush pending work, map the qubits through the qubit map
+ * on the host and make one streaming read of every shard where it lies: no remap, no gather of
+ * amplitudes; the map, the amplitudes and the gradient work states are left exactly as they are.
+ * Both synchronise.  A selected qubit sits on a local position or on a rank position (the top
+ * log2(world) ones).
+ * Marginal: every shard bins its local positions and adds its 2^k_loc bins into the rank's
+ * zero-filled 2^k vector at the indices of its own rank bits (shards of a process in rank order,
+ * no floating-point atomics); one all-reduce of 2^k doubles adds the ranks.
+ * Matrix: blocks between equal rank bits are one read of each shard.  For every non-zero d inside
+ * the selected rank positions (at most 7 steps) rank r pairs with r ^ d and the block between the
+ * two is computed from the own shard and the received one.  When the top local position is not
+ * selected, half a shard moves each way and each rank of a pair sums half of the environment;
+ * when it is selected, a whole shard moves each way and the lower rank computes the block.  Sums
+ * are added in a fixed order (diagonal blocks shard by shard in rank order, then the steps in
+ * ascending d), one all-reduce of 2 * 4^k doubles follows, and the host mirrors the upper triangle:
+ * rho equals its conjugate transpose bitwise and two calls on the same state and layout return
+ * identical doubles.  Device scratch beyond the state's staging buffers: at most 64 MiB of
+ * partial sums, plus one block vector and the result vector. */
+int qsim_dist_marginal_probabilities(qsim_dist* d, const int32_t* qubits, int k, double* out);
+int qsim_dist_reduced_density_matrix(qsim_dist* d, const int32_t* qubits, int k, double* out);
+/* Host-only (no GPU): what the two entries above do for qubit map `perm` (n entries; null: the
+ * identity) in a world of `world` ranks; rdm != 0: for the matrix.  With L = n - log2(world):
+ * info[0] = k_loc, selected physical positions below L; [1] = k_rank, those from L up;
+ * [2], [3], [4], [5] = k_lo, k_hi, slices and work-groups of the shard's own plan, which are
+ * qsim_marginal_plan's for n = L and the k_loc local positions; [6] = cross steps (2^k_rank - 1
+ * for the matrix, 0 for the marginal); [7] = transfers per rank (one send / receive pair per
+ * step); [8], [9] = bytes one rank sends in a call, low and high word; [10] = kernel launches per
+ * shard, at most (a rank that is the lower one of all its pairs); [11] = doubles in the one
+ * all-reduce; [12], [13] = scratch bytes of the partial sums, low and high word (<= 64 MiB; the
+ * block vector and the result vector come on top); [14] = the pair rule: 0 no cross step, 1 half a
+ * shard each way and both ranks compute, 2 a whole shard each way and the lower rank computes;
+ * [15] = work-groups of the two-source kernel (0 without cross steps).  The argument checks and
+ * error codes of the two entries above; a perm that is no permutation or a world that is no
+ * power of two -> QSIM_ERR_INVALID_ARGUMENT. */
+int qsim_dist_marginal_plan(int n_qubits, int world, const int32_t* perm, const int32_t* qubits, int k, int rdm,
+                            int32_t info[16]);
 /* qsim_state_gradient on the sharded state (collective).  Runs the circuit exactly as
  * qsim_dist_run(d, gates, count, flags) would (fresh-state relabel, plan cache; a carried step is
  * flushed first, as by every reader), then *value = <psi|H|psi> as qsim_dist_expectation computes

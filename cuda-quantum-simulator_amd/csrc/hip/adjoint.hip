@@ -4,7 +4,7 @@
 // With phi_k = U_k ... U_1 |psi0>, lambda_k = U_{k+1}^† ... U_N^† H |phi_N> and, for a rotation
 // U_k = exp(-i theta/2 G_k) (G_k = P_target, or |1><1|_control (x) P_target for CRY / CRZ),
 //     dE/dtheta_k = Im <lambda_k| G_k |phi_k>.
-// The backward sweep (capi.hip: qsim_state_gradient) starts from phi = phi_N, lambda = H phi_N and
+// The backward sweep (qsim_state_gradient below) starts from phi = phi_N, lambda = H phi_N and
 // walks the circuit from its last gate to its first: at a rotation it accumulates the bra-ket, then
 // applies U_k^† to both states.  Three kernels serve it:
 //   pauli_apply   dst = H src out of place, one streaming pass per group of terms sharing an x mask
@@ -17,10 +17,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <memory>
+#include <string>
 #include <vector>
 
 #include "device_ops.hpp"
 #include "engine.hpp"
+#include "state.hpp"
 
 namespace qsim_hip {
 
@@ -310,4 +313,237 @@ void launch_adjoint_step(double2* phi, double2* lam, int n, const Generator& g, 
     launch_sum_partials(d_partials, (int)p.chunks, 1, d_out, false, s);
 }
 
+// ---- the gradient on a single-GPU state ----
+// The work states of the backward sweep and room for `count` per-gate results.
+static GradWork& ensure_grad(qsim_state* s, size_t count) {
+    if (!s->grad) s->grad = std::make_unique<GradWork>();
+    GradWork& w = *s->grad;
+    const size_t bytes = sizeof(double2) << s->n;
+    auto grab = [&](void** p, size_t b) {
+        if (*p) return;
+        if (hipMalloc(p, b) != hipSuccess) {
+            (void)hipGetLastError();  // (clear the sticky error: the state itself is intact)
+            *p = nullptr;
+            s->grad.reset();
+            fail(QSIM_ERR_DEVICE, "out of device memory for the gradient work states");
+        }
+    };
+    grab((void**)&w.phi, bytes);
+    grab((void**)&w.lam, bytes);
+    if (count > w.out_cap) {
+        if (w.d_out) {
+            QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+            (void)hipFree(w.d_out);
+            w.d_out = nullptr;
+            w.out_cap = 0;
+        }
+        const size_t cap = std::max<size_t>(count, 256);
+        grab((void**)&w.d_out, cap * sizeof(double));
+        w.out_cap = cap;
+    }
+    return w;
+}
+
+// Inverted non-parameterised gates (execution order) on both work states, the way `flags` says.
+static void grad_apply_segment(qsim_state* s, GradWork& w, const std::vector<Op>& seg, int flags) {
+    if (seg.empty()) return;
+    if (flags & QSIM_RUN_FUSED) {
+        PlanCache::Entry& pe = w.plans.get(seg, s->n, s->stream);
+        const Plan& plan = pe.plan;
+        w.ops.upload(plan.ops.data(), plan.ops.size() * sizeof(TileOp), s->stream);
+        w.stages.upload(plan.stages.data(), plan.stages.size() * sizeof(Stage), s->stream);
+        for (double2* buf : {w.phi, w.lam}) {
+            double2* r = launch_fused(buf, s->n, 1, plan, (const TileOp*)w.ops.ptr, (const Stage*)w.stages.ptr,
+                                      s->stream, &s->timer);
+            if (r != buf) fail(QSIM_ERR_RUNTIME, "a gradient segment planned a relayout pass");
+        }
+    } else {
+        for (const Op& op : seg) {
+            launch_op(w.phi, s->n, 1, op, s->stream, &s->timer);
+            launch_op(w.lam, s->n, 1, op, s->stream, &s->timer);
+        }
+    }
+}
+
+// What the two gradient entry points (here and in pauli_rot.hip) do once the forward pass has run:
+// the outputs zeroed, *value = <psi|H|psi> queued and, with `sweep` (there is something to
+// differentiate), the work states of the backward sweep queued as well: phi = a copy of the state
+// where it lies, lambda = H phi under that layout.  Returns them, or null when the call is already
+// complete (H = 0, or no sweep): the stream is then drained.
+GradWork* gradient_prologue(qsim_state* s, const qsim_pauli_term* terms, size_t nterms, size_t count, bool sweep,
+                            double* value, double* grad) {
+    const int n = s->n;
+    *value = 0.0;
+    for (size_t k = 0; k < count; ++k) grad[k] = 0.0;
+    const int* perm = s->perm.empty() ? nullptr : s->perm.data();
+    const ExpectPlan eplan = lower_expectation(n, terms, nterms, perm);
+    if (eplan.terms.empty()) {  // H = 0 (no terms, or every coefficient cancels): no sweep
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+        return nullptr;
+    }
+    // (the work states first: a failed allocation leaves nothing queued)
+    GradWork* w = sweep ? &ensure_grad(s, count) : nullptr;
+    launch_expectation(s->d, n, 1, eplan, s->expect_terms, s->d_partials, s->d_result, s->stream, &s->timer);
+    QSIM_HIPCHK(hipMemcpyAsync(value, s->d_result, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+    if (!w) {  // the value alone
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+        return nullptr;
+    }
+    QSIM_HIPCHK(hipMemcpyAsync(w->phi, s->d, sizeof(double2) << n, hipMemcpyDeviceToDevice, s->stream));
+    launch_pauli_apply(s->d, w->lam, n, lower_pauli_apply(n, terms, nterms, perm), w->terms, s->stream, &s->timer);
+    return w;
+}
+
 }  // namespace qsim_hip
+
+using namespace qsim_hip;
+
+extern "C" {
+
+int qsim_gate_inverse(const qsim_gate* g, qsim_gate* out) {
+    return guarded([&] {
+        QSIM_REQUIRE(g && out, QSIM_ERR_INVALID_ARGUMENT, "null gate");
+        if (g->type < 0 || g->type >= QSIM_GATE_COUNT)
+            fail(QSIM_ERR_RUNTIME, "Unknown gate type " + std::to_string(g->type));
+        *out = gate_inverse(*g);
+    });
+}
+
+int qsim_gradient_plan(int n_qubits, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms,
+                       size_t nterms, int* n_params, int* n_segments, int* apply_passes) {
+    return guarded([&] {
+        QSIM_REQUIRE(n_params && n_segments && apply_passes, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        check_gradient_args(n_qubits, gates, count, terms, nterms);
+        int params = 0, segments = 0;
+        bool in_segment = false;
+        for (size_t k = 0; k < count; ++k) {
+            if (gate_is_parameterised(gates[k].type)) {
+                ++params;
+                in_segment = false;
+            } else if (params > 0 && !in_segment) {  // (gates before the first parameter are never undone)
+                ++segments;
+                in_segment = true;
+            }
+        }
+        *n_params = params;
+        *n_segments = segments;
+        *apply_passes = (int)lower_pauli_apply(n_qubits, terms, nterms, nullptr).launches;
+    });
+}
+
+int qsim_state_apply_pauli_sum(qsim_state* src, qsim_state* dst, const qsim_pauli_term* terms, size_t count) {
+    return guarded([&] {
+        check_state(src);
+        check_state(dst);
+        QSIM_REQUIRE(terms || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        if (src == dst) fail(QSIM_ERR_INVALID_ARGUMENT, "the Pauli sum is applied out of place: src == dst");
+        if (src->n != dst->n) fail(QSIM_ERR_INVALID_ARGUMENT, "states have different qubit counts");
+        if (src->device != dst->device) fail(QSIM_ERR_INVALID_ARGUMENT, "states live on different devices");
+        DeviceGuard dg(src->device);
+        share_flush(src);
+        // (a handed-out device pointer always sees the identity layout)
+        if (dst->pinned) prep(src, false);
+        const ExpectPlan plan =
+            lower_pauli_apply(src->n, terms, count, src->perm.empty() ? nullptr : src->perm.data());
+        drop_layout(dst);
+        dst->perm = src->perm;
+        QSIM_HIPCHK(hipStreamSynchronize(src->stream));  // src's writes done; dst's stream orders the rest
+        launch_pauli_apply(src->d, dst->d, src->n, plan, dst->expect_terms, dst->stream, &dst->timer);
+        QSIM_HIPCHK(hipStreamSynchronize(dst->stream));
+    });
+}
+
+int qsim_state_inner_product(qsim_state* a, qsim_state* b, double out[2]) {
+    return guarded([&] {
+        check_state(a);
+        check_state(b);
+        QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (a->n != b->n) fail(QSIM_ERR_INVALID_ARGUMENT, "states have different qubit counts");
+        if (a->device != b->device) fail(QSIM_ERR_INVALID_ARGUMENT, "states live on different devices");
+        DeviceGuard dg(a->device);
+        share_flush(a);
+        share_flush(b);
+        if (a->perm != b->perm) {  // one common layout: the identity
+            prep(a, false);
+            prep(b, false);
+        }
+        QSIM_HIPCHK(hipStreamSynchronize(b->stream));  // b's writes done; a's stream orders the rest
+        double* d_out = (double*)a->scratch.get(2 * sizeof(double), a->stream);
+        launch_braket(a->d, b->d, a->n, Generator{}, a->d_partials, d_out, d_out + 1, a->stream, &a->timer);
+        QSIM_HIPCHK(hipMemcpyAsync(out, d_out, 2 * sizeof(double), hipMemcpyDeviceToHost, a->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(a->stream));
+    });
+}
+
+int qsim_state_gradient_release(qsim_state* s) {
+    return guarded([&] {
+        check_state(s);
+        if (!s->grad) return;
+        DeviceGuard dg(s->device);
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+        s->grad.reset();
+    });
+}
+
+int qsim_state_gradient(qsim_state* s, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms,
+                        size_t nterms, int flags, double* value, double* grad) {
+    int rc = guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(value, QSIM_ERR_INVALID_ARGUMENT, "null value");
+        QSIM_REQUIRE(grad || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gradient");
+        check_gradient_args(s->n, gates, count, terms, nterms);
+        DeviceGuard dg(s->device);
+        share_flush(s);
+    });
+    if (rc != QSIM_OK) return rc;
+    // (the sweep below reads the state this run leaves: it runs its own plan whole)
+    struct ShareBlock {
+        qsim_state* s;
+        explicit ShareBlock(qsim_state* st) : s(st) { s->share_block = true; }
+        ~ShareBlock() { s->share_block = false; }
+    } share_block(s);
+    // The forward run is qsim_run itself: the state ends exactly as a plain run leaves it, and
+    // nothing below writes to it.
+    if (count > 0 && (rc = qsim_run(s, gates, count, flags)) != QSIM_OK) return rc;
+    return guarded([&] {
+        DeviceGuard dg(s->device);
+        const int n = s->n;
+        size_t first_param = count;
+        for (size_t k = count; k-- > 0;)
+            if (gate_is_parameterised(gates[k].type)) first_param = k;
+        GradWork* wp = gradient_prologue(s, terms, nterms, count, first_param < count, value, grad);
+        if (!wp) return;  // H = 0, or no parameter: the value alone
+        GradWork& w = *wp;
+        QSIM_HIPCHK(hipMemsetAsync(w.d_out, 0, count * sizeof(double), s->stream));
+        const int th = state_tile_height(s);
+        const TileHeightScope tile_h(th, tile_rb_for(n, th));  // the segments' plans
+        const bool fused_step = adjoint_fused_on();
+        std::vector<Op> seg;
+        for (size_t k = count; k-- > first_param;) {
+            const qsim_gate inv_gate = map_gate(s, gate_inverse(gates[k]));
+            Op inv = lower_gate(inv_gate, n);
+            if (!gate_is_parameterised(gates[k].type)) {
+                inv.src = (int)seg.size();
+                seg.push_back(inv);
+                continue;
+            }
+            grad_apply_segment(s, w, seg, flags);
+            seg.clear();
+            const Generator gen = gate_generator(inv_gate);  // (physical positions)
+            if (k == first_param) {  // nothing is left to differentiate: no un-apply
+                launch_braket(w.lam, w.phi, n, gen, s->d_partials, nullptr, w.d_out + k, s->stream, &s->timer);
+            } else if (fused_step) {
+                launch_adjoint_step(w.phi, w.lam, n, gen, inv, s->d_partials, w.d_out + k, s->stream, &s->timer);
+            } else {
+                launch_braket(w.lam, w.phi, n, gen, s->d_partials, nullptr, w.d_out + k, s->stream, &s->timer);
+                launch_op(w.phi, n, 1, inv, s->stream, &s->timer);
+                launch_op(w.lam, n, 1, inv, s->stream, &s->timer);
+            }
+        }
+        QSIM_HIPCHK(hipMemcpyAsync(grad, w.d_out, count * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+    });
+}
+
+}  // extern "C"

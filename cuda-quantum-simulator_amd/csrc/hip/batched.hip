@@ -24,6 +24,7 @@
 
 #include "device_ops.hpp"
 #include "engine.hpp"
+#include "state.hpp"
 #include "qsim_hip.h"
 
 using namespace qsim_hip;
@@ -319,28 +320,8 @@ struct qsim_batch {
 };
 
 namespace {
-template <typename F>
-int bguard(F&& f) {
-    try {
-        f();
-        return QSIM_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return QSIM_ERR_RUNTIME;
-    }
-}
 void need(const qsim_batch* b) {
     if (!b) fail(QSIM_ERR_INVALID_ARGUMENT, "null batch handle");
-}
-qsim_gate map_gate(const qsim_batch* b, const qsim_gate& g) {
-    qsim_gate m = g;
-    if (!b->perm.empty())
-        for (int j = 0; j < g.nqubits && j < 3; ++j)
-            if (g.qubits[j] >= 0 && g.qubits[j] < b->n) m.qubits[j] = b->perm[g.qubits[j]];
-    return m;
 }
 // The ensemble back in its first buffer (after a pulled run that ended in the second one).
 void settle_in_d0(qsim_batch* b) {
@@ -552,7 +533,7 @@ void canonicalize(qsim_batch* b) {
 extern "C" {
 
 int qsim_batch_create(int n_qubits, int batch_size, qsim_batch** out) {
-    return bguard([&] {
+    return guarded([&] {
         if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
         *out = nullptr;
         if (n_qubits < QSIM_MIN_QUBITS || n_qubits > QSIM_MAX_QUBITS_SINGLE)
@@ -576,11 +557,11 @@ int qsim_batch_create(int n_qubits, int batch_size, qsim_batch** out) {
 }
 
 int qsim_batch_destroy(qsim_batch* b) {
-    return bguard([&] { delete b; });
+    return guarded([&] { delete b; });
 }
 
 int qsim_batch_reset(qsim_batch* b) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         launch_init_basis(b->d, b->n, b->batch, 0, b->stream);
         QSIM_HIPCHK(hipStreamSynchronize(b->stream));
@@ -591,7 +572,7 @@ int qsim_batch_reset(qsim_batch* b) {
 }
 
 int qsim_batch_set_seed(qsim_batch* b, uint64_t seed) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         b->seed = seed;
         b->step = 0;
@@ -600,7 +581,7 @@ int qsim_batch_set_seed(qsim_batch* b, uint64_t seed) {
 }
 
 int qsim_batch_set_trajectory_offset(qsim_batch* b, uint64_t first) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         if (first > (1ull << 40)) fail(QSIM_ERR_INVALID_ARGUMENT, "trajectory offset out of range");
         b->traj0 = first;
@@ -609,7 +590,7 @@ int qsim_batch_set_trajectory_offset(qsim_batch* b, uint64_t first) {
 
 int qsim_batch_run(qsim_batch* b, const qsim_gate* gates, size_t count,
                    const qsim_noise_channel* channels, size_t n_channels, int flags) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         if (!gates && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gate list");
         std::vector<DevChannel> ch;
@@ -620,10 +601,7 @@ int qsim_batch_run(qsim_batch* b, const qsim_gate* gates, size_t count,
                 ch.push_back(DevChannel{c.type, c.qubit, c.probability});
         }
         for (size_t i = 0; i < count; ++i) validate_gate(gates[i], b->n);
-        static const bool fused_env = [] {
-            const char* e = std::getenv("QSIM_BATCH_FUSED");
-            return e == nullptr || std::atoi(e) != 0;
-        }();
+        static const bool fused_env = env_switch("QSIM_BATCH_FUSED", true);
         const bool fused_path = b->n >= 10 && fused_env && !(flags & QSIM_BATCH_PER_GATE) &&
                                 !(flags & QSIM_BATCH_REFERENCE_NOISE);
         if (flags & QSIM_BATCH_REFERENCE_NOISE) canonicalize(b);  // per-pair draws name positions
@@ -875,7 +853,7 @@ int qsim_batch_run(qsim_batch* b, const qsim_gate* gates, size_t count,
 }
 
 int qsim_batch_avg_probabilities(qsim_batch* b, double* dst) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         canonicalize(b);
         const uint64_t N = 1ull << b->n;
@@ -887,7 +865,7 @@ int qsim_batch_avg_probabilities(qsim_batch* b, double* dst) {
 }
 
 int qsim_batch_traj_probabilities(qsim_batch* b, int traj, double* dst) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         canonicalize(b);
         if (traj < 0 || traj >= b->batch) fail(QSIM_ERR_OUT_OF_RANGE, "Invalid trajectory index");
@@ -900,7 +878,7 @@ int qsim_batch_traj_probabilities(qsim_batch* b, int traj, double* dst) {
 }
 
 int qsim_batch_sample(qsim_batch* b, const double* uniforms, int shots, int64_t* out) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         canonicalize(b);
         if (shots < 0) fail(QSIM_ERR_INVALID_ARGUMENT, "n_shots must be non-negative");
@@ -910,7 +888,7 @@ int qsim_batch_sample(qsim_batch* b, const double* uniforms, int shots, int64_t*
 }
 
 int qsim_batch_histogram(qsim_batch* b, const double* uniforms, int shots, int64_t* hist) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         canonicalize(b);
         if (shots < 0) fail(QSIM_ERR_INVALID_ARGUMENT, "n_shots must be non-negative");
@@ -935,7 +913,7 @@ int qsim_batch_histogram(qsim_batch* b, const double* uniforms, int shots, int64
 }
 
 int qsim_batch_traj_state(qsim_batch* b, int traj, double* dst) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         canonicalize(b);
         if (traj < 0 || traj >= b->batch) fail(QSIM_ERR_OUT_OF_RANGE, "Invalid trajectory index");
@@ -948,7 +926,7 @@ int qsim_batch_traj_state(qsim_batch* b, int traj, double* dst) {
 
 // Reads b->d under b->perm: carried frames are applied (materialize), the layout is not restored.
 int qsim_batch_expectation(qsim_batch* b, const qsim_pauli_term* terms, size_t count, double* per_traj) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         if (!per_traj || (count && !terms)) fail(QSIM_ERR_INVALID_ARGUMENT, "null buffer");
         const ExpectPlan plan = lower_expectation(b->n, terms, count, b->perm.empty() ? nullptr : b->perm.data());
@@ -965,7 +943,7 @@ int qsim_batch_expectation(qsim_batch* b, const qsim_pauli_term* terms, size_t c
 }
 
 int qsim_batch_device_ptr(qsim_batch* b, void** dptr) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         canonicalize(b);
         b->basis = false;  // the caller may write through the pointer
@@ -976,7 +954,7 @@ int qsim_batch_device_ptr(qsim_batch* b, void** dptr) {
 }
 
 int qsim_batch_perm(qsim_batch* b, int32_t* perm) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         if (!perm) fail(QSIM_ERR_INVALID_ARGUMENT, "null perm");
         for (int q = 0; q < b->n; ++q) perm[q] = b->perm.empty() ? q : b->perm[q];
@@ -984,7 +962,7 @@ int qsim_batch_perm(qsim_batch* b, int32_t* perm) {
 }
 
 int qsim_batch_last_run(qsim_batch* b, int* passes, int* jit_passes) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         if (passes) *passes = b->last_passes;
         if (jit_passes) *jit_passes = b->last_jit_passes;
@@ -992,7 +970,7 @@ int qsim_batch_last_run(qsim_batch* b, int* passes, int* jit_passes) {
 }
 
 int qsim_batch_sync(qsim_batch* b) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         materialize(b);  // the carried frames are queued work too
         QSIM_HIPCHK(hipStreamSynchronize(b->stream));
@@ -1000,14 +978,14 @@ int qsim_batch_sync(qsim_batch* b) {
 }
 
 int qsim_batch_profile(qsim_batch* b, int enable) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         b->timer.enabled = enable != 0;
     });
 }
 
 int qsim_batch_profile_count(qsim_batch* b, int* n) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         b->timer.resolve();
         *n = (int)b->timer.stats.size();
@@ -1016,7 +994,7 @@ int qsim_batch_profile_count(qsim_batch* b, int* n) {
 
 int qsim_batch_profile_get(qsim_batch* b, int i, char* name, size_t name_len, double* total_ms,
                            int64_t* launches, double* alg_bytes) {
-    return bguard([&] {
+    return guarded([&] {
         need(b);
         b->timer.resolve();
         if (i < 0 || i >= (int)b->timer.stats.size()) fail(QSIM_ERR_OUT_OF_RANGE, "bad index");

@@ -153,7 +153,7 @@ static void open_comm(qsim_dist* d, int world, int rank, const void* unique_id) 
 extern "C" {
 
 int qsim_dist_unique_id(void* id_out) {
-    return dguard([&] {
+    return guarded([&] {
         if (!id_out) fail(QSIM_ERR_INVALID_ARGUMENT, "null id buffer");
         static_assert(sizeof(ncclUniqueId) <= QSIM_DIST_UNIQUE_ID_BYTES, "unique id size");
         ncclUniqueId id;
@@ -165,7 +165,7 @@ int qsim_dist_unique_id(void* id_out) {
 
 int qsim_dist_create(int n_qubits, int rank, int world, const void* unique_id, int device,
                      qsim_dist** out) {
-    return dguard([&] {
+    return guarded([&] {
         if (!out || !unique_id) fail(QSIM_ERR_INVALID_ARGUMENT, "null argument");
         *out = nullptr;
         const int g = log2_exact(world);
@@ -179,7 +179,7 @@ int qsim_dist_create(int n_qubits, int rank, int world, const void* unique_id, i
 }
 
 int qsim_dist_create_virtual(int n_qubits, int world, int device, qsim_dist** out) {
-    return dguard([&] {
+    return guarded([&] {
         if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null argument");
         *out = nullptr;
         const int g = log2_exact(world);
@@ -194,7 +194,7 @@ int qsim_dist_create_virtual(int n_qubits, int world, int device, qsim_dist** ou
 
 int qsim_dist_create_hosted(int n_qubits, int rank, int world, int device, qsim_dist_transport_fn fn,
                             void* ctx, qsim_dist** out) {
-    return dguard([&] {
+    return guarded([&] {
         if (!out || !fn) fail(QSIM_ERR_INVALID_ARGUMENT, "null argument");
         *out = nullptr;
         const int g = log2_exact(world);
@@ -209,7 +209,7 @@ int qsim_dist_create_hosted(int n_qubits, int rank, int world, int device, qsim_
 }
 
 int qsim_dist_virtual_rccl(qsim_dist* d, const void* unique_id) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         if (!d->virt || d->comm) fail(QSIM_ERR_INVALID_ARGUMENT, "needs a virtual object without a communicator");
         if (!unique_id) fail(QSIM_ERR_INVALID_ARGUMENT, "null argument");
@@ -219,7 +219,7 @@ int qsim_dist_virtual_rccl(qsim_dist* d, const void* unique_id) {
 }
 
 int qsim_dist_destroy(qsim_dist* d) {
-    return dguard([&] { delete d; });
+    return guarded([&] { delete d; });
 }
 
 int qsim_dist_reset(qsim_dist* d) {
@@ -240,14 +240,14 @@ int qsim_dist_run(qsim_dist* d, const qsim_gate* gates, size_t count, int flags)
 }
 
 int qsim_dist_remap_bytes(qsim_dist* d, double* sent) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         if (sent) *sent = d->sent_bytes;
     });
 }
 
 int qsim_dist_fused_remaps(qsim_dist* d, int* remaps) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         if (!remaps) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
         *remaps = d->fused_remaps;
@@ -255,7 +255,7 @@ int qsim_dist_fused_remaps(qsim_dist* d, int* remaps) {
 }
 
 int qsim_dist_carried_runs(qsim_dist* d, int* runs) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         if (!runs) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
         *runs = d->carried;
@@ -263,7 +263,7 @@ int qsim_dist_carried_runs(qsim_dist* d, int* runs) {
 }
 
 int qsim_dist_overlapped(qsim_dist* d, int* remaps) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         if (remaps) *remaps = d->overlapped;
     });
@@ -290,7 +290,7 @@ int qsim_dist_barrier(qsim_dist* d) {
 }
 
 int qsim_dist_perm(qsim_dist* d, int32_t* perm) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         for (int q = 0; q < d->n; ++q) perm[q] = d->perm[q];
     });
@@ -385,14 +385,14 @@ int qsim_dist_bcast(qsim_dist* d, double* buf, size_t count) {
 }
 
 int qsim_dist_profile(qsim_dist* d, int enable) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         d->timer.enabled = enable != 0;
     });
 }
 
 int qsim_dist_profile_count(qsim_dist* d, int* n) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         QSIM_HIPCHK(hipSetDevice(d->device));
         d->timer.resolve();
@@ -402,7 +402,7 @@ int qsim_dist_profile_count(qsim_dist* d, int* n) {
 
 int qsim_dist_profile_get(qsim_dist* d, int i, char* name, size_t name_len, double* total_ms,
                           int64_t* launches, double* alg_bytes) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         QSIM_HIPCHK(hipSetDevice(d->device));
         d->timer.resolve();

@@ -515,7 +515,7 @@ extern "C" {
 
 int qsim_dist_gradient(qsim_dist* d, const qsim_gate* gates, size_t count, const qsim_pauli_term* terms,
                        size_t nterms, int flags, double* value, double* grad) {
-    int rc = dguard([&] {
+    int rc = guarded([&] {
         need(d);
         if (!value) fail(QSIM_ERR_INVALID_ARGUMENT, "null value");
         if (!grad && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gradient");
@@ -532,7 +532,7 @@ int qsim_dist_gradient(qsim_dist* d, const qsim_gate* gates, size_t count, const
 }
 
 int qsim_dist_gradient_release(qsim_dist* d) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         if (!d->grad) return;
         QSIM_HIPCHK(hipSetDevice(d->device));
@@ -542,7 +542,7 @@ int qsim_dist_gradient_release(qsim_dist* d) {
 }
 
 int qsim_dist_gradient_memory_bytes(qsim_dist* d, uint64_t* bytes) {
-    return dguard([&] {
+    return guarded([&] {
         need(d);
         if (!bytes) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
         *bytes = 0;
@@ -555,7 +555,7 @@ int qsim_dist_gradient_memory_bytes(qsim_dist* d, uint64_t* bytes) {
 
 int qsim_dist_gradient_plan(int n_qubits, int world, const int32_t* perm, const qsim_gate* gates, size_t count,
                             const qsim_pauli_term* terms, size_t nterms, qsim_dist_gradient_info* out) {
-    return dguard([&] {
+    return guarded([&] {
         if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
         const int g = HostPlanArgs(n_qubits, world).g;
         check_gradient_args(n_qubits, gates, count, terms, nterms);

@@ -201,7 +201,7 @@ int qsim_dist_expectation(qsim_dist* d, const qsim_pauli_term* terms, size_t cou
 int qsim_dist_expectation_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* terms,
                                size_t count, int* local_groups, int* cross_groups, int* transfers, int* launches,
                                uint64_t* bytes_sent_per_rank) {
-    return dguard([&] {
+    return guarded([&] {
         const int L = HostPlanArgs(n_qubits, world).L;
         if (!terms && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
         if (!local_groups || !cross_groups || !transfers || !launches || !bytes_sent_per_rank)

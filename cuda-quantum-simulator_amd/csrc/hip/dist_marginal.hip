@@ -468,7 +468,7 @@ int qsim_dist_reduced_density_matrix(qsim_dist* d, const int32_t* qubits, int k,
 
 int qsim_dist_marginal_plan(int n_qubits, int world, const int32_t* perm, const int32_t* qubits, int k, int rdm,
                             int32_t info[16]) {
-    return dguard([&] {
+    return guarded([&] {
         if (!info) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
         const int L = HostPlanArgs(n_qubits, world).L;
         const DistMarginalPlan p = lower_dist_marginal(n_qubits, L, qubits, k, perm, rdm != 0);

@@ -327,7 +327,7 @@ int qsim_dist_apply_pauli_rotations(qsim_dist* d, const qsim_pauli_term* rots, s
 
 int qsim_dist_pauli_rotation_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* rots,
                                   size_t count, qsim_dist_pauli_rotation_info* out) {
-    return dguard([&] {
+    return guarded([&] {
         if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
         const int L = HostPlanArgs(n_qubits, world).L;
         if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
@@ -338,7 +338,7 @@ int qsim_dist_pauli_rotation_plan(int n_qubits, int world, const int32_t* perm, 
 
 int qsim_dist_pauli_gradient(qsim_dist* d, const qsim_pauli_term* rots, size_t count, const qsim_pauli_term* terms,
                              size_t nterms, double* value, double* grad) {
-    int rc = dguard([&] {
+    int rc = guarded([&] {
         need(d);
         if (!value) fail(QSIM_ERR_INVALID_ARGUMENT, "null value");
         if (!grad && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gradient");
@@ -362,7 +362,7 @@ int qsim_dist_pauli_gradient(qsim_dist* d, const qsim_pauli_term* rots, size_t c
 int qsim_dist_pauli_gradient_plan(int n_qubits, int world, const int32_t* perm, const qsim_pauli_term* rots,
                                   size_t count, const qsim_pauli_term* terms, size_t nterms,
                                   qsim_dist_pauli_gradient_info* out) {
-    return dguard([&] {
+    return guarded([&] {
         if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
         const int L = HostPlanArgs(n_qubits, world).L;
         if (!rots && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null rotation list");

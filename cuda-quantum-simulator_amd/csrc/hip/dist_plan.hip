@@ -18,17 +18,13 @@ namespace qsim_hip {
 
 // QSIM_DIST_COARSE=0: no coarse parts (DStep::coarse; read once)
 static bool coarse_enabled() {
-    static const bool v = [] {
-        const char* e = std::getenv("QSIM_DIST_COARSE");
-        return e == nullptr || std::atoi(e) != 0;
-    }();
+    static const bool v = env_switch("QSIM_DIST_COARSE", true);
     return v;
 }
 // QSIM_DIST_CARRY=1 (experimental, off by default; read per call so tests can switch it): a run's
 // last step is left pending and merged into the next run's first step (run_dist).
 bool carry_enabled() {
-    const char* e = std::getenv("QSIM_DIST_CARRY");
-    return e != nullptr && std::atoi(e) != 0;
+    return env_switch("QSIM_DIST_CARRY", false);
 }
 // The positions of `mask` that pass p's tile touches (all of them for a per-gate step or a tile
 // below 4 free bits: such passes never run as sub-space launches).
@@ -161,14 +157,8 @@ static std::vector<double> score_parallel(size_t count, F&& cost) {
 // (carried into the next run, qsim_dist_run).
 static void mark_overlap(std::vector<DStep>& steps, int L, int world, const std::vector<DStep>& ref,
                          uint64_t carry = 0, const std::vector<Op>* next_ops = nullptr) {
-    static const int enabled = [] {
-        const char* e = std::getenv("QSIM_DIST_OVERLAP");
-        return e ? std::atoi(e) : 1;
-    }();
-    static const int by_plan = [] {
-        const char* e = std::getenv("QSIM_DIST_PIVOT_PLAN");
-        return e ? std::atoi(e) : 1;
-    }();
+    static const int enabled = env_int("QSIM_DIST_OVERLAP", 1);
+    static const int by_plan = env_int("QSIM_DIST_PIVOT_PLAN", 1);
     static const int max_piv = [] {
         const char* e = std::getenv("QSIM_DIST_PIVOTS");
         return e ? std::max(1, std::min(kMaxPivots, std::atoi(e))) : kMaxPivots;
@@ -313,10 +303,7 @@ static int needs_local(const qsim_gate& g) {
 // QSIM_DIST_FULL_REMAP=0 lets a remap move only the globals that must leave (fewer bytes, fewer
 // links); the default swaps all of them (see plan_dist).
 static bool full_remap() {
-    static const bool v = [] {
-        const char* e = std::getenv("QSIM_DIST_FULL_REMAP");
-        return e == nullptr || std::atoi(e) != 0;
-    }();
+    static const bool v = env_switch("QSIM_DIST_FULL_REMAP", true);
     return v;
 }
 
@@ -795,10 +782,7 @@ static bool cycle_pivots(const qsim_gate* gates, size_t count, int n, int g, con
     // 42 / 1-3 gives 4.03 / 3.98 / 4.11 / 3.97x with it against 4.18 / 4.00 / 4.11 / 4.22x from the
     // descent alone — W-HC tiles are dense, a split's free positions number one or two, and the
     // plans re-padded under the chosen sets lose the split anyway)
-    static const bool construct = [] {
-        const char* e = std::getenv("QSIM_DIST_CYCLE_CONSTRUCT");
-        return e != nullptr && std::atoi(e) != 0;
-    }();
+    static const bool construct = env_switch("QSIM_DIST_CYCLE_CONSTRUCT", false);
     if (C <= 3 && construct) {
         std::vector<std::vector<uint64_t>> mA(C), mB(C);
         std::vector<int> use(64, 0);
@@ -888,10 +872,7 @@ static bool cycle_pivots(const qsim_gate* gates, size_t count, int n, int g, con
             }
         if (!tops.empty() && sc[bi] < 1e29) P = tops[bi];
     }
-    static const int sweeps = [] {
-        const char* e = std::getenv("QSIM_DIST_CYCLE_SWEEPS");
-        return e ? std::max(0, std::atoi(e)) : 2;
-    }();
+    static const int sweeps = std::max(0, env_int("QSIM_DIST_CYCLE_SWEEPS", 2));
     for (int sw = 0; sw < sweeps; ++sw)
         for (int j = 0; j < C; ++j) optimise(j);
     static const bool dbg = std::getenv("QSIM_DIST_DEBUG_CYCLE") != nullptr;
@@ -930,10 +911,7 @@ std::vector<DStep> plan_dist(const qsim_gate* gates, size_t count, int n, int g,
     const std::vector<int> perm_in = perm;
     std::vector<DStep> steps = plan_dist_core(gates, count, n, g, rank, perm);
     const int L = n - g;
-    static const int overlap = [] {
-        const char* e = std::getenv("QSIM_DIST_OVERLAP");
-        return e ? std::atoi(e) : 1;
-    }();
+    static const int overlap = env_int("QSIM_DIST_OVERLAP", 1);
     if (!overlap || L < 8 || steps.empty() || steps[0].kind != 0) carry = 0;
     auto same = [&](const PivotMemo& m) {
         return m.n == n && m.g == g && m.carry == carry && m.perm == perm_in && m.gates.size() == count &&
@@ -1096,7 +1074,7 @@ extern "C" {
 int qsim_dist_plan(int n, int world, int rank, const qsim_gate* gates, size_t count,
                    int32_t* perm_inout, qsim_dist_step* steps, size_t step_cap, size_t* n_steps,
                    qsim_op* ops, size_t op_cap, size_t* n_ops) {
-    return dguard([&] {
+    return guarded([&] {
         HostPlanArgs a(n, world, rank, perm_inout);
         const std::vector<DStep> st = plan_dist(gates, count, n, a.g, rank, a.perm);
         size_t si = 0, oi = 0;
@@ -1141,7 +1119,7 @@ int qsim_dist_plan(int n, int world, int rank, const qsim_gate* gates, size_t co
 
 static int plan_passes_impl(int n, int world, int rank, const qsim_gate* gates, size_t count, int32_t* perm_inout,
                             uint64_t* carry_inout, int32_t* passes, size_t cap, size_t* n_steps, int width) {
-    return dguard([&] {
+    return guarded([&] {
         HostPlanArgs a(n, world, rank, perm_inout);
         const uint64_t carry = carry_inout ? *carry_inout : 0ull;
         const std::vector<DStep> st = plan_dist(gates, count, n, a.g, rank, a.perm, carry);
@@ -1200,7 +1178,7 @@ int qsim_dist_plan_passes(int n, int world, int rank, const qsim_gate* gates, si
 }
 
 int qsim_dist_plan_memo_clear(void) {
-    return dguard([&] {
+    return guarded([&] {
         std::lock_guard<std::mutex> l(g_pivot_mu);
         g_pivots.clear();
         g_cycles.clear();
@@ -1209,7 +1187,7 @@ int qsim_dist_plan_memo_clear(void) {
 
 int qsim_dist_slab_map(int n, int world, int rank, const qsim_dist_step* step, int part,
                        int32_t* my_c, int32_t* peer_of, uint64_t* index, size_t index_cap) {
-    return dguard([&] {
+    return guarded([&] {
         const HostPlanArgs a(n, world, rank);
         if (!step || step->kind != 1 || step->k < 1 || step->k > a.g)
             fail(QSIM_ERR_INVALID_ARGUMENT, "not an exchange step");

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "state.hpp"
 #include "qsim_hip.h"
 
 namespace qsim_hip {
@@ -121,20 +122,7 @@ struct XPlan {
 // part < 0: the whole shard; part j: the amplitudes whose pivot bits hold the bits of j.
 XPlan xplan(int L, int rank, const DStep& ex, int part = -1);
 
-// ---- the C entries' guards -------------------------------------------------------------------
-template <typename F>
-int dguard(F&& f) {
-    try {
-        f();
-        return QSIM_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return QSIM_ERR_RUNTIME;
-    }
-}
+// ---- the C entries' prologues (their guard: state.hpp guarded) ---------------------------------
 int log2_exact(int w);
 void check_sizes(int n, int g);
 std::vector<int> checked_perm(int n, const int32_t* perm);  // null: the identity

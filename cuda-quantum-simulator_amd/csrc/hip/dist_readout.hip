@@ -494,7 +494,7 @@ int qsim_dist_measure(qsim_dist* d, int logical_bit, double u, int* result) {
 }
 
 int qsim_dist_sample_plan(int n_qubits, int world, const int32_t* perm, int* chunk_log, uint64_t* localize_mask) {
-    return dguard([&] {
+    return guarded([&] {
         const int L = HostPlanArgs(n_qubits, world).L, c = dist_chunk_log(L);
         if (!perm) fail(QSIM_ERR_INVALID_ARGUMENT, "null qubit map");
         const std::vector<int> p = checked_perm(n_qubits, perm);

@@ -217,7 +217,7 @@ void need(const qsim_dist* d);
 // peers blocked in a collective with this rank are released instead of hanging.
 template <typename F>
 int dguard_comm(qsim_dist* d, F&& f) {
-    const int rc = dguard(std::forward<F>(f));
+    const int rc = guarded(std::forward<F>(f));
     if (rc == QSIM_ERR_DEVICE && d && d->comm && !d->aborted) {
         (void)ncclCommAbort(d->comm);
         d->comm = nullptr;

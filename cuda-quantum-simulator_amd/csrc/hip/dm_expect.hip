@@ -30,6 +30,7 @@
 
 #include "device_ops.hpp"
 #include "engine.hpp"
+#include "state.hpp"
 
 namespace qsim_hip {
 
@@ -150,3 +151,38 @@ void launch_dm_expectation(const double2* rho, const DmExpectPlan& plan, DevBuf&
 }
 
 }  // namespace qsim_hip
+
+// ---- the C entries ----
+using namespace qsim_hip;
+
+// Reads s->d (the current buffer) under s->perm as they are: no prep() / canonicalize(), nothing of
+// the state changes.
+extern "C" int qsim_dm_expectation(qsim_state* s, int n, const qsim_pauli_term* terms, size_t count, double* out) {
+    return guarded([&] {
+        check_dm(s, n);
+        QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        QSIM_REQUIRE(terms || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        DeviceGuard dg(s->device);
+        share_flush(s);  // (pending gates of a run-sharing cycle; the layout may change with them)
+        const DmExpectPlan plan = lower_dm_expectation(n, terms, count, s->perm.empty() ? nullptr : s->perm.data());
+        *out = 0.0;
+        if (plan.rows.empty()) return;
+        double* d_work = (double*)s->scratch.get(dm_expect_work_doubles(plan) * sizeof(double), s->stream);
+        launch_dm_expectation(s->d, plan, s->expect_terms, d_work, s->d_result, s->stream, &s->timer);
+        QSIM_HIPCHK(hipMemcpyAsync(out, s->d_result, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+    });
+}
+
+extern "C" int qsim_dm_expectation_plan(int n, const qsim_pauli_term* terms, size_t count, const int32_t* perm,
+                                        int* groups, int* rows, int* launches, uint64_t* elements) {
+    return guarded([&] {
+        QSIM_REQUIRE(terms || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        QSIM_REQUIRE(groups && rows && launches && elements, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        const DmExpectPlan plan = lower_dm_expectation(n, terms, count, perm);
+        *groups = (int)plan.groups;
+        *rows = (int)plan.rows.size();
+        *launches = (int)plan.launches;
+        *elements = (uint64_t)plan.groups << n;
+    });
+}

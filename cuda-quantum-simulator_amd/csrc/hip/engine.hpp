@@ -27,13 +27,19 @@ struct Error : std::runtime_error {
     Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
 };
 [[noreturn]] inline void fail(int code, const std::string& m) { throw Error(code, m); }
-// Thread-local message returned by qsim_last_error() (capi.hip).
+// Thread-local message returned by qsim_last_error() (state.hip).
 void set_last_error(const char* msg);
 // A boolean switch of the environment, read at every call (so a test or a benchmark runs both
 // settings in one process): unset is `dflt`, else whether the value reads as a non-zero integer.
 inline bool env_switch(const char* name, bool dflt) {
     const char* e = std::getenv(name);
     return e ? std::atoi(e) != 0 : dflt;
+}
+// An integer of the environment (unset: `dflt`), read at every call likewise.  A setting that is
+// fixed for the process keeps the value of either in a function-local static.
+inline int env_int(const char* name, int dflt) {
+    const char* e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
 }
 
 #define QSIM_HIPCHK(call)                                                                   \
@@ -79,6 +85,9 @@ struct Op {
 
 // Lower one reference gate (validated) to an Op.  Throws Error on bad input.
 Op lower_gate(const qsim_gate& g, int n_qubits);
+// A gate list lowered under the labels `perm` (qubit q -> perm[q]; empty: the identity), op i
+// from gate i (src = i).
+std::vector<Op> lower_gates(int n, const qsim_gate* gates, size_t count, const std::vector<int>& perm);
 // Validate a gate against n qubits with the reference's rules (src/Circuit.cpp:16-55).
 void validate_gate(const qsim_gate& g, int n_qubits);
 // Algorithmic HBM bytes of one op over `amps` amplitudes.
@@ -88,7 +97,7 @@ const char* gate_name(int type);
 // ---------------------------------------------------------------------------------------
 // Kernel launch interface (gates.hip)
 // ---------------------------------------------------------------------------------------
-struct Timer;  // per-launch HIP-event attribution (capi.hip)
+struct Timer;  // per-launch HIP-event attribution (state.hip)
 
 // Apply one op to `batch` contiguous trajectories of 2^n amplitudes each.
 void launch_op(double2* st, int n, uint64_t batch, const Op& op, hipStream_t s, Timer* tm);
@@ -249,7 +258,7 @@ Plan plan_permutation_pass(int n, const std::vector<int>& perm);
 // (either may be empty: the identity).
 Plan plan_permutation_pass(int n, const std::vector<int>& from, const std::vector<int>& to);
 bool relayout_forced();  // mode 2: a relayout plan whenever one exists (tests)
-// Run sharing (relayout.hip; driven by capi.hip qsim_run): `copies` consecutive runs of one
+// Run sharing (relayout.hip; driven by run.hip qsim_run): `copies` consecutive runs of one
 // circuit planned as ONE relayout plan and executed piecewise, call by call.  Call j of a cycle
 // launches the longest prefix of not-yet-launched passes whose gates all belong to copies <= j;
 // the requested gates in later passes stay pending until the next call or the next reader.
@@ -327,7 +336,7 @@ LayoutChoice choose_layout(int n, const std::function<std::vector<Op>(const std:
                            int tries, size_t want_alts = 0, double stage_us = 0.0);
 // QSIM_RELABEL_CALIBRATE (default 1) / QSIM_RELABEL_CALIBRATE_MIN_QUBITS (default 26): with
 // inline compilation (QSIM_JIT=2) the first run of a basis state times the model's choice and
-// its alternatives with their circuit-specialised kernels and keeps the fastest (capi.hip).
+// its alternatives with their circuit-specialised kernels and keeps the fastest (first_layout.hip).
 bool relabel_calibrate(int n);
 void calibrate_configure(int mode, int min_qubits);  // negative: unchanged
 bool calibrate_mode_on();  // the calibration mode alone (QSIM_RELABEL_CALIBRATE / qsim_set_calibrate)
@@ -344,7 +353,7 @@ bool layout_cache_load(int n, int kind, const void* key, size_t bytes, std::vect
 void layout_cache_store(int n, int kind, const void* key, size_t bytes, int h, const std::vector<int>& perm);
 bool layout_memo_get(int n, int kind, const void* gates, size_t bytes, std::vector<int>& perm, int* h = nullptr);
 void layout_memo_put(int n, int kind, const void* gates, size_t bytes, const std::vector<int>& perm, int h = -1);
-bool calibrate_heights(int n);  // QSIM_CALIBRATE_HEIGHTS (capi.hip: choose_first_layout)
+bool calibrate_heights(int n);  // QSIM_CALIBRATE_HEIGHTS (first_layout.hip: choose_first_layout)
 // Factor on the predicted cost of a 13-qubit tile (QSIM_LAYOUT_T13, default 1); a scope sets it
 // for the calling thread (and choose_layout hands it to its worker threads).
 double layout_t13();
@@ -374,6 +383,8 @@ int jit_min_qubits();  // smaller states never JIT (QSIM_JIT_MIN_QUBITS, default
 void jit_configure(int mode, int min_qubits);  // < 0 leaves a setting unchanged
 void jit_shutdown();  // stop the background compiler (queued jobs dropped, running one joined)
 std::string jit_source(const Plan& plan);      // empty when the plan has no staged pass
+// A generated source copied out the way the *_jit_source entries return it (len: its length).
+void copy_source(const std::string& src, char* buf, size_t cap, size_t* len);
 bool jit_compile(const std::string& src, std::vector<char>& code, std::string& log);
 // The loaded module for `plan`, or null while it compiles / when JIT does not apply.
 const JitModule* jit_for(JitState& js, const Plan& plan, int n);
@@ -830,7 +841,7 @@ void launch_dist_adjoint_step(double2* own, const double2* peer, const double2* 
                               const Op& inv, double* d_partials, double* d_out, hipStream_t s, Timer* tm);
 
 // ---------------------------------------------------------------------------------------
-// Timing (capi.hip): per-launch HIP events grouped by kernel name.
+// Timing (state.hip): per-launch HIP events grouped by kernel name.
 // ---------------------------------------------------------------------------------------
 struct Timer {
     struct Pending { int slot; hipEvent_t a, b; double bytes; };

@@ -27,6 +27,7 @@
 
 #include "device_ops.hpp"
 #include "engine.hpp"
+#include "state.hpp"
 
 namespace qsim_hip {
 
@@ -308,3 +309,35 @@ void launch_dist_expectation(const double2* own, const double2* peer, int L, int
 }
 
 }  // namespace qsim_hip
+
+// ---- the C entries ----
+using namespace qsim_hip;
+
+// Reads s->d under s->perm as they are: no prep() / canonicalize(), nothing of the state changes.
+extern "C" int qsim_state_expectation(qsim_state* s, const qsim_pauli_term* terms, size_t count, double* out) {
+    return guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        QSIM_REQUIRE(terms || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        DeviceGuard dg(s->device);
+        share_flush(s);  // (pending gates of a run-sharing cycle; the layout may change with them)
+        const ExpectPlan plan = lower_expectation(s->n, terms, count, s->perm.empty() ? nullptr : s->perm.data());
+        *out = 0.0;
+        if (plan.terms.empty()) return;
+        launch_expectation(s->d, s->n, 1, plan, s->expect_terms, s->d_partials, s->d_result, s->stream, &s->timer);
+        QSIM_HIPCHK(hipMemcpyAsync(out, s->d_result, sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+    });
+}
+
+extern "C" int qsim_expectation_plan(int n_qubits, const qsim_pauli_term* terms, size_t count, const int32_t* perm,
+                                     int* passes, int* launches) {
+    return guarded([&] {
+        QSIM_REQUIRE(terms || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        QSIM_REQUIRE(passes && launches, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        const ExpectPlan plan = lower_expectation(n_qubits, terms, count, perm);
+        *passes = (int)plan.groups.size();
+        *launches = (int)plan.launches;
+    });
+}

@@ -266,10 +266,7 @@ static void plan_stages(std::vector<TileOp>& pass_ops, std::vector<int>& pass_sr
     // each time the bit that lets the scan take the most ops (QSIM_STAGE_SEARCH=0: first fit
     // only).  Fewer LDS round trips per pass: the density-matrix passes spend their time in their
     // stages, W-HC 14q DM 39-47 stages per 6-pass plan with first fit.
-    static const bool search = [] {
-        const char* e = std::getenv("QSIM_STAGE_SEARCH");
-        return e == nullptr || std::atoi(e) != 0;
-    }();
+    static const bool search = env_switch("QSIM_STAGE_SEARCH", true);
     auto stage = [&](const std::vector<int>& from, uint32_t allowed) {
         Taken ff = take(from, allowed);
         if (!search || ff.deferred.empty() || rb < 2) return ff;
@@ -347,10 +344,7 @@ static void plan_stages(std::vector<TileOp>& pass_ops, std::vector<int>& pass_sr
     std::vector<int> rem(ops.size());
     for (size_t i = 0; i < rem.size(); ++i) rem[i] = (int)i;
     std::vector<std::pair<uint32_t, std::vector<int>>> seq;  // (register bits, ops) per stage
-    static const int beam_w = [] {  // QSIM_STAGE_BEAM: beam width over stage sequences (0: greedy)
-        const char* e = std::getenv("QSIM_STAGE_BEAM");
-        return e ? std::max(0, std::atoi(e)) : 0;
-    }();
+    static const int beam_w = std::max(0, env_int("QSIM_STAGE_BEAM", 0));  // beam width over stage sequences
     if (search && beam_w > 0) {
         // Beam over stage sequences: states ranked by the ops still to place (then by stages so
         // far, equal at a level); the first state with none left wins (fewest stages found).
@@ -799,11 +793,6 @@ void PlanCache::put(std::vector<Op> ops, int n_qubits, Plan plan, hipStream_t st
     e->ctrl_out = tile_ctrl_out() ? 1 : 0;
     e->used = ++clock;
     entries.push_back(std::move(e));
-}
-
-static int env_int(const char* k, int d) {
-    const char* e = std::getenv(k);
-    return e ? std::atoi(e) : d;
 }
 
 static std::atomic<int> g_tile_h{-1};  // qsim_set_tile_height (-1: not set)
@@ -1559,10 +1548,7 @@ __global__ __launch_bounds__((64 << H) >> RBT, H >= 7 ? 1 : 2) void k_fused_stag
 // +1.5 % on the 28q W-HC sweep); QSIM_FUSED_NT=0 restores the default cache policy.  Read once
 // per process, like the per-gate knobs in gates.hip.
 static bool fused_nt() {
-    static const bool v = [] {
-        const char* e = std::getenv("QSIM_FUSED_NT");
-        return e == nullptr || std::atoi(e) != 0;
-    }();
+    static const bool v = env_switch("QSIM_FUSED_NT", true);
     return v;
 }
 

@@ -124,6 +124,20 @@ Op lower_gate(const qsim_gate& g, int n) {
     return op;
 }
 
+std::vector<Op> lower_gates(int n, const qsim_gate* gates, size_t count, const std::vector<int>& pi) {
+    std::vector<Op> ops;
+    ops.reserve(count);
+    for (size_t i = 0; i < count; ++i) {
+        qsim_gate m = gates[i];
+        if (!pi.empty())  // (an index out of range stays as it is: lower_gate reports it)
+            for (int j = 0; j < m.nqubits && j < 3; ++j)
+                if (m.qubits[j] >= 0 && m.qubits[j] < n) m.qubits[j] = pi[m.qubits[j]];
+        ops.push_back(lower_gate(m, n));
+        ops.back().src = (int)i;
+    }
+    return ops;
+}
+
 double op_alg_bytes(const Op& op, double amps) {
     // bytes = 2 (read+write) x 16 B x amplitudes the op can change  
     const double ctrl = std::ldexp(1.0, -op.ncontrols());
@@ -477,21 +491,17 @@ struct Tune {
     int slice_u_far = 2, far_lo = 20, far_hi = 25, far_mode = 2, far_min_n = 24, far_bmap = 1, bmap = 1;
     bool nt = true;
     Tune() {
-        auto env = [](const char* k, int d) {
-            const char* v = std::getenv(k);
-            return v ? std::atoi(v) : d;
-        };
-        slice_u = env("QSIM_SLICE_U", slice_u);
-        slice_u_far = env("QSIM_SLICE_U_FAR", slice_u_far);
-        far_lo = env("QSIM_SLICE_FAR_LO", far_lo);
-        far_hi = env("QSIM_SLICE_FAR_HI", far_hi);
-        far_mode = env("QSIM_SLICE_FAR_MODE", far_mode);
-        far_min_n = env("QSIM_SLICE_FAR_MIN_QUBITS", far_min_n);
-        far_bmap = env("QSIM_SLICE_FAR_BMAP", far_bmap);
-        bmap = env("QSIM_SLICE_BMAP", bmap);
-        lane_u = env("QSIM_LANE_U", lane_u);
-        diag_u = env("QSIM_DIAG_U", diag_u);
-        nt = env("QSIM_NT", nt ? 1 : 0) != 0;
+        slice_u = env_int("QSIM_SLICE_U", slice_u);
+        slice_u_far = env_int("QSIM_SLICE_U_FAR", slice_u_far);
+        far_lo = env_int("QSIM_SLICE_FAR_LO", far_lo);
+        far_hi = env_int("QSIM_SLICE_FAR_HI", far_hi);
+        far_mode = env_int("QSIM_SLICE_FAR_MODE", far_mode);
+        far_min_n = env_int("QSIM_SLICE_FAR_MIN_QUBITS", far_min_n);
+        far_bmap = env_int("QSIM_SLICE_FAR_BMAP", far_bmap);
+        bmap = env_int("QSIM_SLICE_BMAP", bmap);
+        lane_u = env_int("QSIM_LANE_U", lane_u);
+        diag_u = env_int("QSIM_DIAG_U", diag_u);
+        nt = env_int("QSIM_NT", nt ? 1 : 0) != 0;
     }
 };
 static const Tune& tune() {

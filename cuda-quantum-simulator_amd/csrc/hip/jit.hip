@@ -16,10 +16,12 @@
 #include <hip/hip_runtime.h>
 #include <hip/hiprtc.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <deque>
 #include <memory>
 #include <mutex>
@@ -27,6 +29,7 @@
 #include <thread>
 
 #include "engine.hpp"
+#include "state.hpp"
 
 namespace qsim_hip {
 
@@ -36,14 +39,10 @@ namespace qsim_hip {
 static std::atomic<int> g_jit_mode{-1};        // 0 off, 1 background compile, 2 compile inline
 static std::atomic<int> g_jit_min_qubits{-1};  // smaller states always use the interpreter
 
-static int env_or(const char* k, int d) {
-    const char* e = std::getenv(k);
-    return e ? std::atoi(e) : d;
-}
 int jit_mode() {
     int m = g_jit_mode.load();
     if (m < 0) {
-        m = env_or("QSIM_JIT", 1);
+        m = env_int("QSIM_JIT", 1);
         g_jit_mode.store(m);
     }
     return m;
@@ -51,7 +50,7 @@ int jit_mode() {
 int jit_min_qubits() {
     int m = g_jit_min_qubits.load();
     if (m < 0) {
-        m = env_or("QSIM_JIT_MIN_QUBITS", 20);
+        m = env_int("QSIM_JIT_MIN_QUBITS", 20);
         g_jit_min_qubits.store(m);
     }
     return m;
@@ -282,7 +281,7 @@ struct Gen {
 // 13-qubit tiles only (default), 2 for every multi-stage pass).  Decided from the pass alone, so
 // the generator and the launch (grid = resident workgroups) agree.
 bool jit_pass_pipelined(const FusedPass& p) {
-    static const int v = env_or("QSIM_JIT_PIPE", 1);
+    static const int v = env_int("QSIM_JIT_PIPE", 1);
     if (p.single >= 0 || p.stage_end - p.stage_begin < 2) return false;
     if (p.relayout) return false;  // (the generator has no pipelined relayout store)
     return v >= 2 || (v == 1 && p.h >= 7);
@@ -337,12 +336,12 @@ std::string jb_expr(const Stage& st, int rb, int tile_bits) {
 // consecutive tiles); 1 each XCD streams one contiguous eighth of the tiles; s >= 2: the XCD bits
 // move to tile-id bits s-2 .. s (XCDs interleave at that granularity); -1 bit-reversed ids.
 int jit_xcd() {
-    static const int v = env_or("QSIM_JIT_XCD", 1);
+    static const int v = env_int("QSIM_JIT_XCD", 1);
     return v;
 }
 // CX · real diag · CX triples emitted as one scale (Gen::xor_diag; QSIM_JIT_XOR_DIAG=0: as three ops)
 bool xor_diag_on() {
-    static const bool v = env_or("QSIM_JIT_XOR_DIAG", 1) != 0;
+    static const bool v = env_int("QSIM_JIT_XOR_DIAG", 1) != 0;
     return v;
 }
 std::string tile_id_expr() {
@@ -419,7 +418,7 @@ void gen_pass(std::ostringstream& out, const Plan& plan, const FusedPass& p, int
           << "  const unsigned long long per = ntiles >> 3, gx = G >> 3;\n"
           << "  unsigned long long it = 0;\n"
           ;
-        if (env_or("QSIM_JIT_PIPE_ORDER", 1) == 1)  // each workgroup streams one contiguous range (default)
+        if (env_int("QSIM_JIT_PIPE_ORDER", 1) == 1)  // each workgroup streams one contiguous range (default)
             o << "  const bool cw = (ntiles % G) == 0ull;\n  const unsigned long long tpw = ntiles / G;\n"
               << "  auto tile_at = [&](unsigned long long i) { return cw ? b * tpw + i : i * G + b; };\n"
               << "  auto tile_ok = [&](unsigned long long i) { return cw ? i < tpw : (i * G + b < ntiles); };\n";
@@ -565,7 +564,7 @@ static std::vector<char> jit_selection(const Plan& plan) {
 std::string jit_source(const Plan& plan) {
     std::ostringstream out;
     bool any = false;
-    out << (env_or("QSIM_JIT_NT", 1) ? kPreludeNT : kPreludeT) << kPrelude;
+    out << (env_int("QSIM_JIT_NT", 1) ? kPreludeNT : kPreludeT) << kPrelude;
     const std::vector<char> sel = jit_selection(plan);
     for (size_t i = 0; i < plan.passes.size(); ++i) {
         if (!sel[i]) continue;
@@ -745,3 +744,69 @@ const JitModule* jit_for(JitState& js, const Plan& plan, int n) {
 }
 
 }  // namespace qsim_hip
+
+// ---- the C entries ----
+namespace qsim_hip {
+void copy_source(const std::string& src, char* buf, size_t cap, size_t* len) {
+    if (len) *len = src.size();
+    if (buf && cap) {
+        const size_t m = std::min(cap - 1, src.size());
+        std::memcpy(buf, src.data(), m);
+        buf[m] = 0;
+    }
+}
+// hipRTC over a generated source (empty: nothing to compile); the size of the code object.
+static void build_source(const std::string& src, size_t* code_bytes) {
+    std::vector<char> code;
+    std::string log;
+    if (!src.empty() && !jit_compile(src, code, log)) fail(QSIM_ERR_RUNTIME, "hipRTC: " + log);
+    if (code_bytes) *code_bytes = code.size();
+}
+static void check_circuit_args(int n_qubits, const qsim_gate* gates, size_t count) {
+    QSIM_REQUIRE(gates || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gate list");
+    if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+}
+}  // namespace qsim_hip
+
+using namespace qsim_hip;
+
+extern "C" {
+
+int qsim_set_jit(int mode, int min_qubits) {
+    return guarded([&] {
+        if (mode > 2) fail(QSIM_ERR_INVALID_ARGUMENT, "jit mode must be 0 (off), 1 (background) or 2 (inline)");
+        jit_configure(mode, min_qubits);
+    });
+}
+
+int qsim_jit_shutdown(void) {
+    return guarded([&] { jit_shutdown(); });
+}
+
+int qsim_jit_source(int n_qubits, const qsim_gate* gates, size_t count, char* buf, size_t cap,
+                    size_t* len) {
+    return guarded([&] {
+        check_circuit_args(n_qubits, gates, count);
+        copy_source(jit_source(plan_fused(lower_gates(n_qubits, gates, count, {}), n_qubits)), buf, cap, len);
+    });
+}
+
+int qsim_jit_build(int n_qubits, const qsim_gate* gates, size_t count, size_t* code_bytes) {
+    return guarded([&] {
+        check_circuit_args(n_qubits, gates, count);
+        build_source(jit_source(plan_fused(lower_gates(n_qubits, gates, count, {}), n_qubits)), code_bytes);
+    });
+}
+
+int qsim_jit_build_relayout(int n_qubits, const qsim_gate* gates, size_t count, size_t* code_bytes) {
+    return guarded([&] {
+        check_circuit_args(n_qubits, gates, count);
+        for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n_qubits);
+        auto lower = [&](const std::vector<int>& pi) { return lower_gates(n_qubits, gates, count, pi); };
+        RelayoutChoice rc;
+        if (!plan_relayout(n_qubits, lower, SIZE_MAX, rc)) fail(QSIM_ERR_RUNTIME, "no relayout plan");
+        build_source(jit_source(rc.plan), code_bytes);
+    });
+}
+
+}  // extern "C"

@@ -46,6 +46,7 @@
 
 #include "device_ops.hpp"
 #include "engine.hpp"
+#include "state.hpp"
 
 namespace qsim_hip {
 
@@ -404,3 +405,50 @@ void rdm_finish(const MarginalPlan& p, const double* raw, double* out) {
 }
 
 }  // namespace qsim_hip
+
+// ---- the C entries ----
+using namespace qsim_hip;
+
+// Both read s->d under s->perm as they are: no prep() / canonicalize(), nothing of the state changes.
+static void run_marginal(qsim_state* s, const int32_t* qubits, int k, bool rdm, double* out) {
+    check_state(s);
+    QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
+    DeviceGuard dg(s->device);
+    share_flush(s);  // (pending gates of a run-sharing cycle; the layout may change with them)
+    const MarginalPlan plan = lower_marginal(s->n, qubits, k, s->perm.empty() ? nullptr : s->perm.data(), rdm);
+    const size_t out_bytes = (rdm ? (size_t)2 << (2 * k) : (size_t)1 << k) * sizeof(double);
+    const size_t part_bytes = (plan.scratch_bytes + 255) & ~(size_t)255;
+    char* buf = (char*)s->scratch.get(part_bytes + out_bytes, s->stream);
+    double* d_out = (double*)(buf + part_bytes);
+    launch_marginal(s->d, plan, (double*)buf, d_out, s->stream, &s->timer);
+    std::vector<double> raw;
+    if (rdm) raw.resize(out_bytes / sizeof(double));
+    QSIM_HIPCHK(hipMemcpyAsync(rdm ? raw.data() : out, d_out, out_bytes, hipMemcpyDeviceToHost, s->stream));
+    QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+    if (rdm) rdm_finish(plan, raw.data(), out);
+}
+
+extern "C" int qsim_state_marginal_probabilities(qsim_state* s, const int32_t* qubits, int k, double* out) {
+    return guarded([&] { run_marginal(s, qubits, k, false, out); });
+}
+
+extern "C" int qsim_state_reduced_density_matrix(qsim_state* s, const int32_t* qubits, int k, double* out) {
+    return guarded([&] { run_marginal(s, qubits, k, true, out); });
+}
+
+extern "C" int qsim_marginal_plan(int n_qubits, const int32_t* qubits, int k, const int32_t* perm, int rdm,
+                                  int32_t info[8]) {
+    return guarded([&] {
+        QSIM_REQUIRE(info, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        const MarginalPlan p = lower_marginal(n_qubits, qubits, k, perm, rdm != 0);
+        info[0] = p.k_lo;
+        info[1] = p.k_hi;
+        info[2] = (int32_t)p.slices;
+        info[3] = (int32_t)p.groups;
+        info[4] = (int32_t)(p.scratch_bytes & 0xffffffffull);
+        info[5] = (int32_t)(p.scratch_bytes >> 32);
+        info[6] = p.launches;
+        info[7] = 0;
+    });
+}

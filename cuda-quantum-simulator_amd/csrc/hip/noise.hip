@@ -237,10 +237,6 @@ __device__ __forceinline__ uint64_t xcd_block(int mode) {
     if (mode == 1 && (G & 7ull) == 0ull) return (b & 7ull) * (G >> 3) + (b >> 3);
     return b;
 }
-static int env_bmap(const char* k, int dflt) {  // (read per launch: tests switch it)
-    const char* e = std::getenv(k);
-    return e ? std::atoi(e) : dflt;
-}
 
 template <bool CHECK>
 __global__ __launch_bounds__(256) void k_noise_units(UArgs a, unsigned int* bad) {
@@ -359,10 +355,7 @@ void launch_noise_after_gate(double2* st, int n, const std::vector<NoiseChan>& c
     // trajectory faster for the push alone (0.137 vs 0.140 ms, profiles/r05/batch_unit/), but in
     // the two-stream step two are: 1.953-1.958 M -> 1.976-1.982 M trajectory-gates/s over two
     // runs each, four trajectories 1.956 M (r6p run))
-    static const int unit_log_env = [] {
-        const char* e = std::getenv("QSIM_NOISE_UNIT_LOG");
-        return e ? std::atoi(e) : 16;
-    }();
+    static const int unit_log_env = env_int("QSIM_NOISE_UNIT_LOG", 16);
     const int log_unit = std::max(log_ppt, unit_log_env);
     const uint64_t pairs = batch << log_ppt, idx0 = traj0 << log_ppt;
     const uint64_t units = ((idx0 + pairs - 1) >> log_unit) - (idx0 >> log_unit) + 1;
@@ -379,7 +372,7 @@ void launch_noise_after_gate(double2* st, int n, const std::vector<NoiseChan>& c
     for (size_t c0 = 0; c0 < chans.size(); c0 += kMaxUnitChannels) {
         UArgs u{};
         u.st = st;
-        u.bmap = env_bmap("QSIM_NOISE_BMAP", 1);
+        u.bmap = env_int("QSIM_NOISE_BMAP", 1);
         u.pairs = pairs;
         u.idx0 = idx0;
         u.log_ppt = log_ppt;
@@ -847,7 +840,7 @@ static GnArgs gn_args(double2* st, int n, uint64_t traj0, const Op* op, const st
     *used_out = used;
     const char* sk = std::getenv("QSIM_NOISE_TILE_SKIP");  // (measurement only)
     a.skip = sk ? std::atoi(sk) : 0;
-    a.bmap = env_bmap("QSIM_NOISE_BMAP", 1);
+    a.bmap = env_int("QSIM_NOISE_BMAP", 1);
     return a;
 }
 
@@ -1447,7 +1440,7 @@ void launch_pull_gate(const double2* src, double2* dst, int n, uint64_t batch, c
     a.dst = dst;
     a.words = words;
     a.amps = amps;
-    a.bmap = fuse ? 0 : env_bmap("QSIM_PULL_BMAP", 0);
+    a.bmap = fuse ? 0 : env_int("QSIM_PULL_BMAP", 0);
     a.kind = op ? op->kind : -1;
     if (op) {
         a.sub = op->sub;

@@ -34,6 +34,7 @@
 
 #include "device_ops.hpp"
 #include "engine.hpp"
+#include "state.hpp"
 
 namespace qsim_hip {
 
@@ -280,3 +281,85 @@ void launch_pauli_adjoint_step(double2* phi, double2* lam, int n, const PauliRot
 }
 
 }  // namespace qsim_hip
+
+// ---- the C entries: rotations and their adjoint gradient on a single-GPU state ----
+using namespace qsim_hip;
+
+extern "C" {
+
+int qsim_state_apply_pauli_rotations(qsim_state* s, const qsim_pauli_term* rots, size_t count) {
+    return guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(rots || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        if (count == 0) return;
+        DeviceGuard dg(s->device);
+        share_flush(s);  // (pending gates of a run-sharing cycle; the layout may change with them)
+        // (the lowering checks every mask of the sequence: nothing of it is launched before)
+        const PauliRotPlan plan =
+            lower_pauli_rotations(s->n, rots, count, s->perm.empty() ? nullptr : s->perm.data());
+        s->basis = false;
+        launch_pauli_rotations(s->d, s->n, plan, s->expect_terms, s->stream, &s->timer);
+    });
+}
+
+int qsim_pauli_rotation_plan(int n_qubits, const qsim_pauli_term* rots, size_t count, const int32_t* perm,
+                             int* passes, int* launches) {
+    return guarded([&] {
+        QSIM_REQUIRE(rots || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        QSIM_REQUIRE(passes && launches, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        const PauliRotPlan plan = lower_pauli_rotations(n_qubits, rots, count, perm);
+        *passes = (int)plan.passes;
+        *launches = (int)plan.launches;
+    });
+}
+
+int qsim_pauli_gradient_plan(int n_qubits, const qsim_pauli_term* rots, size_t count,
+                             const qsim_pauli_term* terms, size_t nterms, const int32_t* perm, int* steps,
+                             int* apply_passes) {
+    return guarded([&] {
+        QSIM_REQUIRE(rots || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        QSIM_REQUIRE(terms || nterms == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        QSIM_REQUIRE(steps && apply_passes, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        const PauliRotPlan plan = lower_pauli_rotations(n_qubits, rots, count, perm);
+        const ExpectPlan aplan = lower_pauli_apply(n_qubits, terms, nterms, perm);
+        *steps = aplan.terms.empty() ? 0 : (int)plan.rots.size();  // (H == 0: no sweep)
+        *apply_passes = (int)aplan.launches;
+    });
+}
+
+int qsim_state_pauli_gradient(qsim_state* s, const qsim_pauli_term* rots, size_t count,
+                              const qsim_pauli_term* terms, size_t nterms, double* value, double* grad) {
+    int rc = guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(value, QSIM_ERR_INVALID_ARGUMENT, "null value");
+        QSIM_REQUIRE(grad || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gradient");
+        QSIM_REQUIRE(rots || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null rotation list");
+        QSIM_REQUIRE(terms || nterms == 0, QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        // (the observable before the sequence is applied; the sequence's masks: by that call)
+        check_pauli_masks(s->n, terms, nterms, "Pauli term");
+    });
+    if (rc != QSIM_OK) return rc;
+    // The forward pass is qsim_state_apply_pauli_rotations itself: the state ends exactly as that
+    // call alone leaves it, and nothing below writes to it.
+    if ((rc = qsim_state_apply_pauli_rotations(s, rots, count)) != QSIM_OK) return rc;
+    return guarded([&] {
+        DeviceGuard dg(s->device);
+        share_flush(s);  // (count == 0: nothing above has flushed)
+        const int n = s->n;
+        GradWork* wp = gradient_prologue(s, terms, nterms, count, count > 0, value, grad);
+        if (!wp) return;  // H = 0, or no rotation: the value alone
+        GradWork& w = *wp;
+        const PauliRotPlan plan =
+            lower_pauli_rotations(n, rots, count, s->perm.empty() ? nullptr : s->perm.data());
+        // every rotation its own step, last to first; the first rotation undoes nothing
+        for (size_t k = count; k-- > 0;)
+            launch_pauli_adjoint_step(w.phi, w.lam, n, plan.rots[k], k > 0, s->d_partials, w.d_out + k, s->stream,
+                                      &s->timer);
+        QSIM_HIPCHK(hipMemcpyAsync(grad, w.d_out, count * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+    });
+}
+
+}  // extern "C"

@@ -15,6 +15,7 @@
 
 #include "device_ops.hpp"
 #include "engine.hpp"
+#include "state.hpp"
 
 namespace qsim_hip {
 
@@ -371,3 +372,83 @@ void launch_avg_probabilities(const double2* st, int n, uint64_t batch, double* 
 }
 
 }  // namespace qsim_hip
+
+// ---- the C entries: readout of a single-GPU state ----
+using namespace qsim_hip;
+
+extern "C" {
+
+int qsim_state_probabilities(qsim_state* s, double* dst) {
+    return guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(dst, QSIM_ERR_INVALID_ARGUMENT, "null destination");
+        DeviceGuard dg(s->device);
+        prep(s, false);
+        const uint64_t N = 1ull << s->n;
+        double* d_p = (double*)s->scratch.get(N * sizeof(double), s->stream);
+        launch_probabilities(s->d, N, d_p, s->stream);
+        QSIM_HIPCHK(hipMemcpyAsync(dst, d_p, N * sizeof(double), hipMemcpyDeviceToHost, s->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+    });
+}
+
+int qsim_state_total_probability(qsim_state* s, double* out) {
+    return guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        DeviceGuard dg(s->device);
+        share_flush(s);
+        *out = reduce_norm(s->d, s->n, -1, s->d_partials, s->d_result, s->stream);
+    });
+}
+
+int qsim_state_prob_bit_zero(qsim_state* s, int bit, double* out) {
+    return guarded([&] {
+        check_state(s);
+        QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (bit < 0 || bit >= s->n) fail(QSIM_ERR_INVALID_ARGUMENT, "bit out of range");
+        DeviceGuard dg(s->device);
+        prep(s, false);
+        *out = reduce_norm(s->d, s->n, bit, s->d_partials, s->d_result, s->stream);
+    });
+}
+
+int qsim_state_max_abs_diff(qsim_state* a, qsim_state* b, double* out) {
+    return guarded([&] {
+        check_state(a);
+        check_state(b);
+        QSIM_REQUIRE(out, QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (a->n != b->n) fail(QSIM_ERR_INVALID_ARGUMENT, "states have different qubit counts");
+        if (a->device != b->device) fail(QSIM_ERR_INVALID_ARGUMENT, "states live on different devices");
+        DeviceGuard dg(a->device);
+        prep(a, false);  // both in the identity layout
+        prep(b, false);
+        QSIM_HIPCHK(hipStreamSynchronize(a->stream));  // a's writes done; b's stream orders the rest
+        *out = a == b ? 0.0 : reduce_max_abs_diff(a->d, b->d, a->n, b->d_partials, b->d_result, b->stream);
+    });
+}
+
+int qsim_state_collapse(qsim_state* s, int bit, int result, double scale) {
+    return guarded([&] {
+        check_state(s);
+        if (bit < 0 || bit >= s->n) fail(QSIM_ERR_INVALID_ARGUMENT, "bit out of range");
+        if (result != 0 && result != 1) fail(QSIM_ERR_INVALID_ARGUMENT, "result must be 0 or 1");
+        DeviceGuard dg(s->device);
+        prep(s, true);
+        launch_collapse(s->d, s->n, bit, result, scale, s->stream);
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+    });
+}
+
+int qsim_state_sample(qsim_state* s, const double* uniforms, int shots, int64_t* out) {
+    return guarded([&] {
+        check_state(s);
+        if (shots <= 0) fail(QSIM_ERR_INVALID_ARGUMENT, "n_shots must be positive");
+        QSIM_REQUIRE(uniforms && out, QSIM_ERR_INVALID_ARGUMENT, "null buffer");
+        DeviceGuard dg(s->device);
+        prep(s, false);
+        sample_indices(s->d, s->n, 1, uniforms, shots, out, s->stream, s->scratch);
+    });
+}
+
+}  // extern "C"

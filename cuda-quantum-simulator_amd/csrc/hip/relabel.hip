@@ -9,7 +9,7 @@
 // permutation that minimises the predicted cost of the plan's tiles (layout_cost.hpp, fitted to
 // the probes by scripts/fit_layout_cost.py), and from then on applies every gate to the permuted
 // qubits.  The permutation is undone by a fused SWAP network before anything reads or touches the
-// amplitudes by index (capi.hip: canonicalize) — so results are exactly those of the
+// amplitudes by index (state.hip: canonicalize) — so results are exactly those of the
 // unpermuted run up to the SWAPs' data movement (which is exact).
 #include <algorithm>
 #include <atomic>
@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "engine.hpp"
+#include "state.hpp"
 #include "layout_cost.hpp"
 
 namespace qsim_hip {
@@ -35,12 +36,10 @@ namespace qsim_hip {
 static std::atomic<int> g_relabel{-1}, g_relabel_min{-1};
 static void relabel_defaults() {
     if (g_relabel.load() < 0) {
-        const char* e = std::getenv("QSIM_RELABEL");
-        g_relabel.store(e ? std::atoi(e) : 1);
+        g_relabel.store(env_int("QSIM_RELABEL", 1));
     }
     if (g_relabel_min.load() < 0) {
-        const char* e = std::getenv("QSIM_RELABEL_MIN_QUBITS");
-        g_relabel_min.store(e ? std::atoi(e) : 26);
+        g_relabel_min.store(env_int("QSIM_RELABEL_MIN_QUBITS", 26));
     }
 }
 bool relabel_enabled(int n) {
@@ -114,22 +113,17 @@ void layout_memo_put(int n, int kind, const void* gates, size_t bytes, const std
 // inline compilation): the first run of a basis state also times 13-qubit-tile candidates
 // against 12-qubit ones (or the reverse) unless a tile height was set explicitly.
 bool calibrate_heights(int n) {
-    static const int v = [] {
-        const char* e = std::getenv("QSIM_CALIBRATE_HEIGHTS");
-        return e ? std::atoi(e) : 1;
-    }();
+    static const int v = env_int("QSIM_CALIBRATE_HEIGHTS", 1);
     return v != 0 && relabel_calibrate(n) && !tile_height_is_set();
 }
 
 static std::atomic<int> g_calib{-1}, g_calib_min{-1};
 bool relabel_calibrate(int n) {
     if (g_calib.load() < 0) {
-        const char* e = std::getenv("QSIM_RELABEL_CALIBRATE");
-        g_calib.store(e ? std::atoi(e) : 1);
+        g_calib.store(env_int("QSIM_RELABEL_CALIBRATE", 1));
     }
     if (g_calib_min.load() < 0) {
-        const char* e = std::getenv("QSIM_RELABEL_CALIBRATE_MIN_QUBITS");
-        g_calib_min.store(e ? std::atoi(e) : 26);
+        g_calib_min.store(env_int("QSIM_RELABEL_CALIBRATE_MIN_QUBITS", 26));
     }
     return g_calib.load() != 0 && n >= g_calib_min.load() && jit_mode() == 2;
 }
@@ -144,10 +138,7 @@ void calibrate_configure(int mode, int min_qubits) {
 }
 
 int relabel_tries() {
-    static const int v = [] {
-        const char* e = std::getenv("QSIM_RELABEL_TRIES");
-        return e ? std::max(0, std::atoi(e)) : 7;
-    }();
+    static const int v = std::max(0, env_int("QSIM_RELABEL_TRIES", 7));
     return v;
 }
 
@@ -387,3 +378,32 @@ LayoutChoice choose_layout(int n, const std::function<std::vector<Op>(const std:
 }
 
 }  // namespace qsim_hip
+
+// ---- the C entries ----
+using namespace qsim_hip;
+
+extern "C" int qsim_set_relabel(int mode, int min_qubits) {
+    return guarded([&] {
+        if (mode > 1) fail(QSIM_ERR_INVALID_ARGUMENT, "relabel mode must be 0 (off) or 1 (on)");
+        relabel_configure(mode, min_qubits);
+    });
+}
+
+extern "C" int qsim_set_calibrate(int mode, int min_qubits) {
+    return guarded([&] { calibrate_configure(mode, min_qubits); });
+}
+
+extern "C" int qsim_plan_relabel(int n_qubits, const qsim_gate* gates, size_t count, int32_t* perm,
+                                 double* cost_before_us, double* cost_after_us) {
+    return guarded([&] {
+        QSIM_REQUIRE(gates || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gate list");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
+        for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n_qubits);
+        auto lower = [&](const std::vector<int>& pi) { return lower_gates(n_qubits, gates, count, pi); };
+        const LayoutChoice lc = choose_layout(n_qubits, lower, relabel_tries());
+        if (perm)
+            for (int q = 0; q < n_qubits; ++q) perm[q] = lc.perm.empty() ? q : lc.perm[q];
+        if (cost_before_us) *cost_before_us = lc.cost_before;
+        if (cost_after_us) *cost_after_us = lc.cost_after;
+    });
+}

@@ -34,6 +34,7 @@
 #include <unordered_set>
 
 #include "engine.hpp"
+#include "state.hpp"
 
 namespace qsim_hip {
 
@@ -41,11 +42,6 @@ namespace {
 
 constexpr int kTile = 12;  // 12-qubit tiles (h = 6): two 64 KiB workgroups per CU
 constexpr int kRun = 4;    // qubits shared by consecutive tiles (the next pass's 256 B run)
-
-int env_int(const char* k, int d) {
-    const char* e = std::getenv(k);
-    return e ? std::atoi(e) : d;
-}
 
 uint64_t op_mask(const Op& op) {
     uint64_t m = op.cmask | (1ull << op.t0);
@@ -835,21 +831,12 @@ void exec_plan_host(const Plan& plan, int n, std::vector<cd>& st, size_t first =
 extern "C" int qsim_plan_exec_host(int n_qubits, const qsim_gate* gates, size_t count, int mode, double* amps,
                                    int32_t* perm, int* passes) {
     using namespace qsim_hip;
-    try {
+    return guarded([&] {
         if (n_qubits < 10 || n_qubits > 26) fail(QSIM_ERR_INVALID_ARGUMENT, "host execution: 10..26 qubits");
         if (!amps || (!gates && count)) fail(QSIM_ERR_INVALID_ARGUMENT, "null argument");
         const int n = n_qubits;
         for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n);
-        auto lower = [&](const std::vector<int>& pi) {
-            std::vector<Op> ops;
-            for (size_t i = 0; i < count; ++i) {
-                qsim_gate m = gates[i];
-                for (int j = 0; j < m.nqubits && j < 3; ++j) m.qubits[j] = pi[m.qubits[j]];
-                ops.push_back(lower_gate(m, n));
-                ops.back().src = (int)i;
-            }
-            return ops;
-        };
+        auto lower = [&](const std::vector<int>& pi) { return lower_gates(n, gates, count, pi); };
         std::vector<int> pi(n);
         for (int q = 0; q < n; ++q) pi[q] = q;
         Plan plan;
@@ -869,7 +856,7 @@ extern "C" int qsim_plan_exec_host(int n_qubits, const qsim_gate* gates, size_t 
                 amps[2 * i + 1] = st[i].imag();
             }
             if (passes) *passes = (int)plan.passes.size();
-            return QSIM_OK;
+            return;
         }
         if (mode == 1) {
             RelayoutChoice rc;
@@ -899,48 +886,25 @@ extern "C" int qsim_plan_exec_host(int n_qubits, const qsim_gate* gates, size_t 
         if (perm)
             for (int q = 0; q < n; ++q) perm[q] = pi[q];
         if (passes) *passes = (int)plan.passes.size();
-        return QSIM_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return QSIM_ERR_RUNTIME;
-    }
+    });
 }
 
 extern "C" int qsim_plan_relayout(int n_qubits, const qsim_gate* gates, size_t count, int32_t* perm, int* passes,
                                   double* predicted_us) {
     using namespace qsim_hip;
-    try {
+    return guarded([&] {
         if (n_qubits < 1 || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
         if (!gates && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gate list");
         const int n = n_qubits;
         for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n);
-        auto lower = [&](const std::vector<int>& pi) {
-            std::vector<Op> ops;
-            for (size_t i = 0; i < count; ++i) {
-                qsim_gate m = gates[i];
-                for (int j = 0; j < m.nqubits && j < 3; ++j) m.qubits[j] = pi[m.qubits[j]];
-                ops.push_back(lower_gate(m, n));
-                ops.back().src = (int)i;
-            }
-            return ops;
-        };
+        auto lower = [&](const std::vector<int>& pi) { return lower_gates(n, gates, count, pi); };
         RelayoutChoice rc;
         const bool ok = plan_relayout(n, lower, SIZE_MAX, rc);
         if (passes) *passes = ok ? (int)rc.plan.passes.size() : 0;
         if (predicted_us) *predicted_us = ok ? rc.cost_us : 0.0;
         if (perm)
             for (int q = 0; q < n; ++q) perm[q] = ok ? rc.perm[q] : q;
-        return QSIM_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return QSIM_ERR_RUNTIME;
-    }
+    });
 }
 
 namespace qsim_hip {
@@ -949,16 +913,7 @@ namespace {
 // circuit's relayout plan where relayout plans are on and one exists, else the fixed-layout plan
 // under the identity labels.
 void host_single_plan(int n, const qsim_gate* gates, size_t count, std::vector<int>& perm, Plan& plan) {
-    auto lower = [&](const std::vector<int>& pi) {
-        std::vector<Op> ops;
-        for (size_t i = 0; i < count; ++i) {
-            qsim_gate m = gates[i];
-            for (int j = 0; j < m.nqubits && j < 3; ++j) m.qubits[j] = pi[m.qubits[j]];
-            ops.push_back(lower_gate(m, n));
-            ops.back().src = (int)i;
-        }
-        return ops;
-    };
+    auto lower = [&](const std::vector<int>& pi) { return lower_gates(n, gates, count, pi); };
     const TileHeightScope scope(6, tile_rb_for(n, 6));
     perm.resize(n);
     for (int q = 0; q < n; ++q) perm[q] = q;
@@ -976,7 +931,7 @@ void host_single_plan(int n, const qsim_gate* gates, size_t count, std::vector<i
 extern "C" int qsim_plan_share_host(int n_qubits, const qsim_gate* gates, size_t count, int copies, int calls,
                                     double* amps, int32_t* passes_per_call, int32_t* pending_per_call) {
     using namespace qsim_hip;
-    try {
+    return guarded([&] {
         if (n_qubits < 10 || n_qubits > 26) fail(QSIM_ERR_INVALID_ARGUMENT, "host execution: 10..26 qubits");
         if (!amps || !gates || count == 0 || calls < 0) fail(QSIM_ERR_INVALID_ARGUMENT, "bad argument");
         const int n = n_qubits;
@@ -1029,9 +984,7 @@ extern "C" int qsim_plan_share_host(int n_qubits, const qsim_gate* gates, size_t
         if (armed && cyc_calls > 0) {  // flush: the pending gates under the current layout
             std::vector<Op> ops;
             for (int g : share_pending(sp, next, cyc_calls)) {
-                qsim_gate m = gates[(size_t)g % count];
-                for (int j = 0; j < m.nqubits && j < 3; ++j) m.qubits[j] = cur[m.qubits[j]];
-                ops.push_back(lower_gate(m, n));
+                ops.push_back(lower_gates(n, &gates[(size_t)g % count], 1, cur)[0]);
                 ops.back().src = (int)ops.size() - 1;
             }
             if (!ops.empty()) {
@@ -1044,20 +997,13 @@ extern "C" int qsim_plan_share_host(int n_qubits, const qsim_gate* gates, size_t
             amps[2 * i] = a.real();
             amps[2 * i + 1] = a.imag();
         }
-        return QSIM_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return QSIM_ERR_RUNTIME;
-    }
+    });
 }
 
 extern "C" int qsim_plan_share_info(int n_qubits, const qsim_gate* gates, size_t count, int copies, int* joint_passes,
                                     int* single_passes, int32_t* pass_copy, size_t cap) {
     using namespace qsim_hip;
-    try {
+    return guarded([&] {
         if (n_qubits < 10 || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
         if (!gates || count == 0) fail(QSIM_ERR_INVALID_ARGUMENT, "bad argument");
         for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n_qubits);
@@ -1070,14 +1016,7 @@ extern "C" int qsim_plan_share_info(int n_qubits, const qsim_gate* gates, size_t
         if (joint_passes) *joint_passes = ok ? (int)sp.plan.passes.size() : 0;
         if (single_passes) *single_passes = (int)single.passes.size();
         for (size_t k = 0; ok && pass_copy && k < cap && k < sp.pass_copy.size(); ++k) pass_copy[k] = sp.pass_copy[k];
-        return QSIM_OK;
-    } catch (const Error& e) {
-        set_last_error(e.what());
-        return e.code;
-    } catch (const std::exception& e) {
-        set_last_error(e.what());
-        return QSIM_ERR_RUNTIME;
-    }
+    });
 }
 
 extern "C" int qsim_set_run_share(int mode, int copies) {

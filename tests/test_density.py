@@ -239,7 +239,7 @@ def test_specialised_kernels_match_oracle(qsim, oracle, gpu_ready, n, seed):
 
 def test_relabeled_plan_has_fewer_passes(qsim):
     """Host-only (qsim_dm_plan_info with QSIM_DM_PLAN_RELABELED): the first-run index-bit labels
-    (capi.hip dm_choose_layout) plan the bench's DM circuit into fewer passes than the identity."""
+    (density.hip dm_choose_layout) plan the bench's DM circuit into fewer passes than the identity."""
     import ctypes
     from qsim_amd import _lib
     n = 14
@@ -260,7 +260,7 @@ def test_relabeled_plan_has_fewer_passes(qsim):
 @pytest.mark.parametrize("n,depth,seed,timed", [(8, 30, 21, False), (9, 16, 22, False), (8, 24, 23, True)])
 def test_relabeled_runs_match_oracle(qsim, oracle, gpu_ready, n, depth, seed, timed):
     """16 / 18 index bits: the first fused run of a reset rho takes relabeled index bits
-    (capi.hip qsim_dm_run; timed: the candidates timed on the device, specialised kernels); a
+    (density.hip qsim_dm_run; timed: the candidates timed on the device, specialised kernels); a
     second run keeps them (its ops mapped through the labels); readers restore the identity first.
     Every step equals the oracle at 1e-12, and a reset + rerun (the memoised labels) gives the
     same rho."""

@@ -125,7 +125,7 @@ def test_pinned_state_is_never_relabeled(qsim, oracle, gpu_ready):
     forced, so an unpinned state would be relabeled) sees the canonical state without calling
     devicePtr() again (reference include/StateVector.cuh:66-124: devicePtr() is the state), and the
     raw kernel entry on it acts on the right qubit.  Pinned states run the identity layout in place
-    (capi.hip qsim_run), so no second buffer and no copy-back either."""
+    (run.hip qsim_run), so no second buffer and no copy-back either."""
     from qsim_amd import _lib
     from qsim_amd.plan import set_jit, set_relayout
     set_relayout(2, 20)  # forced relayout plan at 22 qubits (taken by an unpinned state)

@@ -1,4 +1,4 @@
-"""Layout-aware qubit relabeling (csrc/hip/relabel.hip, qsim_run in capi.hip).
+"""Layout-aware qubit relabeling (csrc/hip/relabel.hip, qsim_run in run.hip).
 
 The first fused run of a basis state may run the whole circuit under a logical -> physical qubit
 permutation chosen for the plan's tile layouts; every entry that reads or writes amplitudes by

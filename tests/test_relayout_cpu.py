@@ -74,7 +74,7 @@ def test_relayout_kernels_compile_for_gfx950(qsim):
 @pytest.mark.parametrize("n,seed", [(16, 1), (20, 2)])
 def test_one_pass_identity_restore(qsim, n, seed):
     """The identity-layout restore before index-based readers is one gate-free relayout pass
-    (capi.hip canonicalize): every amplitude lands at its logical index."""
+    (state.hip canonicalize): every amplitude lands at its logical index."""
     import ctypes
     from qsim_amd import _lib
     rng = np.random.default_rng(seed)

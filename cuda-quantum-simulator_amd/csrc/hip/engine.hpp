@@ -625,6 +625,69 @@ void launch_marginal(const double2* st, const MarginalPlan& plan, double* d_part
 // Host: the upper triangle of raw in the caller's numbering, the diagonal's imaginary part zeroed,
 // mirrored into the lower one (out == out^dagger bitwise).
 void rdm_finish(const MarginalPlan& plan, const double* raw, double* out);
+// The second kernel of these readers (marginal.hip), shared with dm_marginal.hip: out[place(t)] =
+// sum over s < S of partials[s * T + t], t < T, added in a fixed order; place: bit i of t lands on
+// bit dst[i] (nbits == 0: the identity).  Asynchronous.
+struct FoldMap {
+    int nbits;
+    int8_t dst[24];
+};
+void launch_fold(const double* partials, uint32_t T, uint32_t S, const FoldMap& map, double* out, hipStream_t s);
+
+// Marginals, reduced density matrices and the fidelity <psi|rho|psi> of a density matrix, read where
+// rho lies (dm_marginal.hip).  rho of n qubits is a 2n-bit state: logical bit q is the column bit of
+// qubit q, bit q + n its row bit; perm maps the 2n logical bits to physical positions (null:
+// identity).  Both subset readers are one gather-reduce over address generators (masks over the 2n
+// physical positions):
+//     out[o] = sum over b < 2^(n-k) of buf[G_out(o) | G_sum(b)],  G(v) = OR of gen[i] over the set bits i of v
+// complex for the matrix, the real part for the marginal.  Matrix: out index o = a << k | a' (row-
+// major rho_A[a][a']), out_gen[j] = 1 << perm[q_j] (bit j of a'), out_gen[k + j] = 1 << perm[q_j + n]
+// (bit j of a).  Marginal: out_gen[j] = both positions of q_j.  sum_gen: both positions of every
+// unselected qubit, ascending.  All generators (n for the marginal, n + k for the matrix) are sorted by
+// their lowest position: the lowest nt <= 8 are a work-group's thread bits, the other sum generators are looped
+// over by each thread (2^s_log slices of them over work-groups), the other out generators choose
+// the work-group.
+constexpr int kDmGatherThreadBits = 8;  // 256 threads
+constexpr int kDmGatherGroupsLog = 10;  // work-groups aimed at
+struct DmGatherGen {
+    uint64_t mask;
+    int out_bit;  // bit of the caller's out index, -1: a sum generator
+};
+struct DmMarginalPlan {
+    int n = 0, k = 0;
+    bool rdm = false;
+    std::vector<uint64_t> out_gen, sum_gen;  // in the caller's bit order / by ascending qubit
+    std::vector<DmGatherGen> sorted;         // all of them by lowest position
+    int nt = 0;                              // thread bits: sorted[0 .. nt)
+    int s_log = 0;                           // slices of the looped sum generators
+    uint64_t elements = 0, groups = 1, scratch_bytes = 0;
+    int launches = 2;
+};
+// Throws Error as lower_marginal does (the same messages): n outside [1, QSIM_DM_MAX_QUBITS], a perm
+// that is no permutation of the 2n bits, a duplicate qubit, k above kRdmMaxQubits (matrix) or n, a
+// null list with k > 0 (invalid argument); a qubit outside [0, n) (out of range).
+DmMarginalPlan lower_dm_marginal(int n, const int32_t* qubits, int k, const int* perm, bool rdm);
+// d_out: 2^k doubles (marginal) or 2 * 4^k (matrix, row-major re/im) in the caller's bit order;
+// d_partials: plan.scratch_bytes.  Reads rho only.  Asynchronous.
+void launch_dm_marginal(const double2* rho, const DmMarginalPlan& plan, double* d_partials, double* d_out,
+                        hipStream_t s, Timer* tm);
+// Fidelity: *d_out = Re sum_ij conj(psi_i) rho[i][j] psi_j, one streaming pass over the 4^n elements
+// in physical address order.  A run is 2^c contiguous elements; its t_r row bits and t_c column
+// bits need 2^t_r + 2^t_c entries of psi, staged in LDS per run (c = min(2n, 12), one less when all
+// twelve are of one kind so the tables stay within kDmFidelityTable entries).
+constexpr unsigned kDmFidelityGroups = 512;  // work-groups (a state of more runs: several per group)
+constexpr int kDmFidelityTable = 2052;       // >= 2^11 + 2^1
+struct DmFidelityPlan {
+    int n = 0, c = 0, t_r = 0, t_c = 0;
+    int8_t qubit[2 * QSIM_DM_MAX_QUBITS];  // physical position -> its qubit
+    uint32_t row_mask = 0;                  // physical positions that are row bits
+    uint64_t runs = 1;
+    unsigned groups = 1;
+};
+DmFidelityPlan lower_dm_fidelity(int n, const int* perm);
+// d_psi: device copy of psi (2^n); d_partials: plan.groups doubles.
+void launch_dm_fidelity(const double2* rho, const double2* d_psi, const DmFidelityPlan& plan, double* d_partials,
+                        double* d_out, hipStream_t s, Timer* tm);
 
 // Pauli-sum expectation values Re Tr(rho H) of a density matrix (dm_expect.hip).  Terms are merged
 // and grouped by logical x mask (one generalised diagonal of rho, 2^n elements, per group) and a

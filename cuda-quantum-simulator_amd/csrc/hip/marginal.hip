@@ -173,14 +173,13 @@ __global__ __launch_bounds__(256) void k_marginal_partial(const double2* __restr
     }
 }
 
+}  // namespace
+
 // out[place(t)] = sum over s < S of partials[s * T + t], t < T, in a fixed order: a work-group
 // takes tx = 2^tx_log consecutive t and splits the S rows over its 256 / tx thread rows, thread
 // row y adding s = y, y + cy, ...; thread row 0 then adds the rows' sums in order.  place: bit i of
-// t lands on bit dst[i] (nbits == 0: the identity).
-struct FoldMap {
-    int nbits;
-    int8_t dst[24];
-};
+// t lands on bit dst[i] (nbits == 0: the identity).  (FoldMap, launch_fold: engine.hpp.)
+namespace {
 __global__ __launch_bounds__(256) void k_fold_partials(const double* __restrict__ partials, uint32_t T, uint32_t S,
                                                        int tx_log, FoldMap map, double* __restrict__ out) {
     __shared__ double red[256];
@@ -204,6 +203,8 @@ __global__ __launch_bounds__(256) void k_fold_partials(const double* __restrict_
     }
 }
 
+}  // namespace
+
 void launch_fold(const double* partials, uint32_t T, uint32_t S, const FoldMap& map, double* out, hipStream_t s) {
     int tx_log = 0;
     while (tx_log < 6 && (1u << (tx_log + 1)) <= T) ++tx_log;
@@ -211,6 +212,8 @@ void launch_fold(const double* partials, uint32_t T, uint32_t S, const FoldMap& 
     hipLaunchKernelGGL(k_fold_partials, dim3((T + tx - 1) / tx), dim3(256), 0, s, partials, T, S, tx_log, map, out);
     QSIM_HIPCHK(hipGetLastError());
 }
+
+namespace {
 
 struct RdmArgs {
     int p;                // panel bits

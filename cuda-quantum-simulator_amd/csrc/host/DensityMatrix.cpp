@@ -57,6 +57,46 @@ double DensityMatrix::expectation(const PauliSum& observable) const {
     return e;
 }
 
+std::vector<double> DensityMatrix::marginalProbabilities(const std::vector<int>& qubits) const {
+    if (qubits.size() > 20) throw std::invalid_argument("at most 20 qubits in a marginal");
+    std::vector<double> out(size_t(1) << qubits.size());
+    check(qsim_dm_marginal_probabilities(rho_.handle(), n_qubits_, qubits.data(), (int)qubits.size(), out.data()));
+    return out;
+}
+
+std::vector<std::complex<double>> DensityMatrix::reducedDensityMatrix(const std::vector<int>& qubits) const {
+    if (qubits.size() > 6) throw std::invalid_argument("at most 6 qubits in a reduced density matrix");
+    std::vector<std::complex<double>> out(size_t(1) << (2 * qubits.size()));
+    // std::complex<double> is layout-compatible with double[2] ([complex.numbers.general]).
+    check(qsim_dm_reduced_density_matrix(rho_.handle(), n_qubits_, qubits.data(), (int)qubits.size(),
+                                         reinterpret_cast<double*>(out.data())));
+    return out;
+}
+
+double DensityMatrix::subsystemPurity(const std::vector<int>& qubits) const {
+    double tr2 = 0.0;
+    for (const auto& v : reducedDensityMatrix(qubits)) tr2 += std::norm(v);
+    return tr2;
+}
+
+double DensityMatrix::subsystemEntropy(const std::vector<int>& qubits, bool renyi2) const {
+    const std::vector<std::complex<double>> a = reducedDensityMatrix(qubits);
+    const int dim = 1 << qubits.size();
+    if (renyi2) return hermitianEntropy(a, dim, true);  // -log2 sum |rho_A[a][a']|^2
+    std::vector<std::complex<double>> h(a.size());
+    auto at = [&](int r, int c) { return a[(size_t)r * dim + c]; };
+    for (int r = 0; r < dim; ++r)
+        for (int c = 0; c < dim; ++c) h[(size_t)r * dim + c] = 0.5 * (at(r, c) + std::conj(at(c, r)));
+    return hermitianEntropy(h, dim, false);
+}
+
+double DensityMatrix::fidelity(const std::vector<std::complex<double>>& psi) const {
+    if (psi.size() != getDimension()) throw std::invalid_argument("State vector size mismatch");
+    double f = 0.0;
+    check(qsim_dm_fidelity(rho_.handle(), n_qubits_, reinterpret_cast<const double*>(psi.data()), &f));
+    return f;
+}
+
 bool DensityMatrix::isValid(double tolerance) const {
     if (std::abs(trace() - 1.0) > tolerance) return false;
     const double pur = purity();

@@ -207,6 +207,11 @@ _sig(hip, "qsim_dm_init_maximally_mixed", [_P, c_int])
 _sig(hip, "qsim_dm_expectation", [_P, c_int, POINTER(qsim_pauli_term), c_size_t, POINTER(c_double)])
 _sig(hip, "qsim_dm_expectation_plan", [c_int, POINTER(qsim_pauli_term), c_size_t, POINTER(c_int32), POINTER(c_int),
                                        POINTER(c_int), POINTER(c_int), POINTER(c_uint64)])
+_sig(hip, "qsim_dm_marginal_probabilities", [_P, c_int, POINTER(c_int32), c_int, _P])
+_sig(hip, "qsim_dm_reduced_density_matrix", [_P, c_int, POINTER(c_int32), c_int, _P])
+_sig(hip, "qsim_dm_fidelity", [_P, c_int, _P, POINTER(c_double)])
+_sig(hip, "qsim_dm_marginal_plan", [c_int, POINTER(c_int32), c_int, POINTER(c_int32), c_int, POINTER(c_int32),
+                                    POINTER(c_uint64), POINTER(c_uint64)])
 
 # ---- multi-GPU (sharded) state
 class qsim_op(Structure):

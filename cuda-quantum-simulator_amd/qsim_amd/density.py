@@ -75,6 +75,59 @@ class DensityMatrix:
     def trace(self) -> float: return float(np.sum(self.getProbabilities()))
     def purity(self) -> float: return self._sv.getTotalProbability()  # sum |rho_ij|^2 (:147-167)
 
+    # Readout of a subset of qubits and the fidelity with a pure state, reduced on the device where
+    # rho lies (csrc/hip/dm_marginal.hip; no reference counterpart): like expectation(), no readback
+    # of the 4^n elements and no layout restore, linear in whatever the buffer holds (nothing is
+    # mirrored or symmetrised), bitwise reproducible.  Qubit q is index bit q; the k qubits are
+    # distinct, in any order, and bit j of an output index is qubits[j].  ValueError on a duplicate
+    # or too many qubits, IndexError on a bad qubit (StateVector.marginalProbabilities' errors).
+    def marginalProbabilities(self, qubits) -> np.ndarray:
+        """out[m] = sum_b Re rho[(m, b)][(m, b)] over the values b of the other qubits: 2^k doubles,
+        k <= n (k = 0: the trace); 2^n elements of rho are read (qsim_dm_marginal_probabilities)."""
+        arr, k = self._sv._qubit_list(qubits, 20)
+        out = np.empty(1 << k, dtype=np.float64)
+        _lib.check(_lib.hip.qsim_dm_marginal_probabilities(self._sv.handle, self._n, arr, k, _ptr(out)))
+        return out
+
+    def reducedDensityMatrix(self, qubits) -> np.ndarray:
+        """rho_A of k <= 6 qubits as a 2^k x 2^k complex128 array, rho_A[a, a'] = sum_b
+        rho[(a, b)][(a', b)]: the partial trace over the other qubits, reading 2^(n+k) elements
+        (qsim_dm_reduced_density_matrix).  With all n <= 6 qubits in order it is getMatrix()."""
+        arr, k = self._sv._qubit_list(qubits, 6)
+        out = np.empty((1 << k, 1 << k), dtype=np.complex128)
+        _lib.check(_lib.hip.qsim_dm_reduced_density_matrix(self._sv.handle, self._n, arr, k, _ptr(out)))
+        return out
+
+    def subsystemPurity(self, qubits) -> float:
+        """sum |rho_A[a][a']|^2 of the k <= 6 qubits (purity()'s definition, on rho_A)."""
+        rho = self.reducedDensityMatrix(qubits)
+        return float(np.sum(rho.real ** 2 + rho.imag ** 2))
+
+    def subsystemEntropy(self, qubits, renyi2: bool = False) -> float:
+        """Von Neumann entropy in bits of the k <= 6 qubits' state, -sum l log2 l over
+        numpy.linalg.eigvalsh((rho_A + rho_A^dagger) / 2) (eigenvalues below 1e-300 contribute 0);
+        renyi2: -log2 subsystemPurity instead.  For a mixed rho this is not an entanglement measure;
+        with all n <= 6 qubits it is the entropy of the state itself."""
+        rho = self.reducedDensityMatrix(qubits)
+        if renyi2:
+            return float(-np.log2(np.sum(rho.real ** 2 + rho.imag ** 2)))
+        ev = np.linalg.eigvalsh((rho + rho.conj().T) / 2)
+        ev = ev[ev >= 1e-300]
+        return float(-np.sum(ev * np.log2(ev)))
+
+    def fidelity(self, psi) -> float:
+        """Re <psi|rho|psi> = Re sum_ij conj(psi_i) rho[i][j] psi_j in one streaming read of rho
+        (qsim_dm_fidelity).  psi: 2^n complex amplitudes, or a StateVector of n qubits (its toHost());
+        used as given, not normalised.  ValueError when the size differs."""
+        if isinstance(psi, StateVector):
+            psi = psi.toHost()
+        a = np.ascontiguousarray(psi, dtype=np.complex128)
+        if a.shape != (1 << self._n,):
+            raise ValueError("State vector size mismatch")
+        f = _c.c_double()
+        _lib.check(_lib.hip.qsim_dm_fidelity(self._sv.handle, self._n, _ptr(a), _c.byref(f)))
+        return f.value
+
     def isValid(self, tolerance: float = 1e-10) -> bool:
         if abs(self.trace() - 1.0) > tolerance:
             return False
@@ -137,6 +190,14 @@ class DensityMatrixSimulator:
     def getProbabilities(self) -> np.ndarray: return self._rho.getProbabilities()
     def getDensityMatrix(self) -> np.ndarray: return self._rho.getMatrix()
     def expectation(self, observable) -> float: return self._rho.expectation(observable)
+    def marginalProbabilities(self, qubits) -> np.ndarray: return self._rho.marginalProbabilities(qubits)
+    def reducedDensityMatrix(self, qubits) -> np.ndarray: return self._rho.reducedDensityMatrix(qubits)
+    def subsystemPurity(self, qubits) -> float: return self._rho.subsystemPurity(qubits)
+
+    def subsystemEntropy(self, qubits, renyi2: bool = False) -> float:
+        return self._rho.subsystemEntropy(qubits, renyi2)
+
+    def fidelity(self, psi) -> float: return self._rho.fidelity(psi)
     def getPurity(self) -> float: return self._rho.purity()
     def getTrace(self) -> float: return self._rho.trace()
     def getNumQubits(self) -> int: return self._rho.getNumQubits()

@@ -217,6 +217,28 @@ def marginal_plan(n: int, qubits, perm=None, rdm: bool = False) -> dict:
             "scratch_bytes": (info[4] & 0xffffffff) | (info[5] << 32), "launches": info[6]}
 
 
+def dm_marginal_plan(n: int, qubits, perm=None, rdm: bool = False) -> dict:
+    """How DensityMatrix.marginalProbabilities (rdm: reducedDensityMatrix) of these qubits lowers
+    under the layout perm of the 2n index bits (logical -> physical, column bit q, row bit q + n;
+    None: identity), host only (qsim_dm_marginal_plan).  Both readers evaluate
+    out[o] = sum_b buf[G_out(o) | G_sum(b)], G(v) the OR of the generators at the set bits of v:
+    out_gen, one address mask per bit of the out index (the matrix: o = a << k | a'), sum_gen, one per
+    unlisted qubit; elements of rho read, work_groups of the first kernel, kernel launches,
+    scratch_bytes of the partial sums, slices of the sum and thread_bits.  The readers' argument
+    checks."""
+    qs = [int(q) for q in qubits]
+    arr = (ctypes.c_int32 * len(qs))(*qs) if qs else None
+    info = (ctypes.c_int32 * 8)()
+    out_gen = (ctypes.c_uint64 * max(1, 2 * len(qs)))()
+    sum_gen = (ctypes.c_uint64 * max(1, n))()
+    _lib.check(_lib.hip.qsim_dm_marginal_plan(n, arr, len(qs), _perm_arg(2 * n, perm), 1 if rdm else 0, info,
+                                              out_gen, sum_gen))
+    return {"elements": (info[0] & 0xffffffff) | (info[1] << 32), "work_groups": info[2], "launches": info[3],
+            "scratch_bytes": info[4], "slices": info[5], "thread_bits": info[6],
+            "out_gen": [int(g) for g in out_gen[:(2 if rdm else 1) * len(qs)]],
+            "sum_gen": [int(g) for g in sum_gen[:n - len(qs)]]}
+
+
 def hermitian_entropy(rho, renyi2: bool = False) -> float:
     """The entropy in bits of a density matrix (at most 64 x 64) by the C++ layer's host routine,
     the cyclic Jacobi sweep behind qsim::StateVector::entanglementEntropy (qsim_hermitian_entropy;

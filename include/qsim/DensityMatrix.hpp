@@ -42,6 +42,26 @@ public:
     // when the observable's qubit count differs.  No reference counterpart.
     double expectation(const PauliSum& observable) const;
 
+    // Readout of a subset of qubits and the fidelity with a pure state, reduced on the device where
+    // rho lies (qsim_dm_marginal_probabilities / qsim_dm_reduced_density_matrix / qsim_dm_fidelity;
+    // no reference counterpart): no readback of the 4^n elements, no layout restore, linear in
+    // whatever the buffer holds (nothing is mirrored or symmetrised), bitwise reproducible.  Qubit
+    // q is index bit q; the k qubits are distinct and in any order, and bit j of an output index is
+    // qubits[j].  std::invalid_argument on a duplicate or too many qubits, std::out_of_range on a
+    // bad qubit (StateVector's exceptions).
+    // out[m] = sum_b Re rho[(m, b)][(m, b)]: 2^k doubles, k <= n (k = 0: the trace).
+    std::vector<double> marginalProbabilities(const std::vector<int>& qubits) const;
+    // rho_A[a][a'] = sum_b rho[(a, b)][(a', b)] of the k <= 6 qubits, 2^k x 2^k row-major.
+    std::vector<std::complex<double>> reducedDensityMatrix(const std::vector<int>& qubits) const;
+    double subsystemPurity(const std::vector<int>& qubits) const;  // sum |rho_A[a][a']|^2
+    // Von Neumann entropy in bits of (rho_A + rho_A^dagger) / 2 by hermitianEntropy (StateVector.hpp);
+    // renyi2: -log2 subsystemPurity.  For a mixed rho this is not an entanglement measure; with all
+    // n <= 6 qubits it is the entropy of the state itself.
+    double subsystemEntropy(const std::vector<int>& qubits, bool renyi2 = false) const;
+    // Re sum_ij conj(psi_i) rho[i][j] psi_j in one streaming read of rho; psi (2^n amplitudes) is
+    // used as given, not normalised.  std::invalid_argument when its size differs.
+    double fidelity(const std::vector<std::complex<double>>& psi) const;
+
     Amplitude* getDevicePtr() { return rho_.devicePtr(); }
     StateVector& state() { return rho_; }
     const StateVector& state() const { return rho_; }
@@ -62,6 +82,12 @@ public:
     std::vector<double> getProbabilities() const { return rho_.getProbabilities(); }
     std::vector<std::complex<double>> getDensityMatrix() const { return rho_.getMatrix(); }
     double expectation(const PauliSum& observable) const { return rho_.expectation(observable); }
+    // DensityMatrix's readout of a subset of qubits and its fidelity, on the device.
+    std::vector<double> marginalProbabilities(const std::vector<int>& q) const { return rho_.marginalProbabilities(q); }
+    std::vector<std::complex<double>> reducedDensityMatrix(const std::vector<int>& q) const { return rho_.reducedDensityMatrix(q); }
+    double subsystemPurity(const std::vector<int>& q) const { return rho_.subsystemPurity(q); }
+    double subsystemEntropy(const std::vector<int>& q, bool renyi2 = false) const { return rho_.subsystemEntropy(q, renyi2); }
+    double fidelity(const std::vector<std::complex<double>>& psi) const { return rho_.fidelity(psi); }
     double getPurity() const { return rho_.purity(); }
     double getTrace() const { return rho_.trace(); }
     int measureQubit(int qubit);  // index bit `qubit` (src/DensityMatrix.cu:374-406)

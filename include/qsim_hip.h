@@ -586,6 +586,43 @@ int qsim_dm_expectation(qsim_state* rho, int n_qubits, const qsim_pauli_term* te
  * outside [1, QSIM_DM_MAX_QUBITS] -> QSIM_ERR_INVALID_ARGUMENT. */
 int qsim_dm_expectation_plan(int n_qubits, const qsim_pauli_term* terms, size_t count, const int32_t* perm,
                              int* groups, int* rows, int* launches, uint64_t* elements);
+/* Marginal probabilities and reduced density matrices of k distinct qubits of rho, and the fidelity
+ * with a pure state, reduced on the device where rho lies (no reference counterpart).  Qubits as in
+ * qsim_state_marginal_probabilities: qubit q is index bit q, the list may be in any order and bit j
+ * of an output index is qubit qubits[j].  With b over the values of the n - k unlisted qubits:
+ *   marginal: out[m] = sum_b Re rho[(m, b)][(m, b)], 2^k doubles, 0 <= k <= n (k == 0: the trace);
+ *   matrix:   out = rho_A, 2^k x 2^k row-major, interleaved re/im (2 * 4^k doubles), 0 <= k <=
+ *             min(n, 6): rho_A[a][a'] = sum_b rho[(a, b)][(a', b)];
+ *   fidelity: *out = Re sum_ij conj(psi_i) rho[i][j] psi_j, psi: 2^n host amplitudes (re/im), used
+ *             as given (not normalised).
+ * Like qsim_dm_expectation all three are linear functionals of whatever the buffer holds: every
+ * element the formula names is summed, nothing is mirrored or symmetrised (for k == n <= 6 the
+ * matrix is the buffer itself and the marginal its diagonal).  The matrix reads 2^(n+k) of the 4^n
+ * elements, the marginal 2^n, the fidelity streams all of them once.  Pending gates of a run-sharing
+ * cycle are flushed, addresses are mapped through the state's current index-bit layout on the host,
+ * and the layout (qsim_state_perm), the current buffer and the elements are left exactly as they
+ * are.  Sums are added in a fixed order (no floating-point atomics): bitwise reproducible.  All
+ * synchronise.  A duplicate qubit, k above the cap, a null pointer (qubits only with k > 0), a state
+ * that is not rho of n_qubits -> QSIM_ERR_INVALID_ARGUMENT; a qubit < 0 or >= n ->
+ * QSIM_ERR_OUT_OF_RANGE. */
+int qsim_dm_marginal_probabilities(qsim_state* rho, int n_qubits, const int32_t* qubits, int k, double* out);
+int qsim_dm_reduced_density_matrix(qsim_state* rho, int n_qubits, const int32_t* qubits, int k, double* out);
+int qsim_dm_fidelity(qsim_state* rho, int n_qubits, const double* psi, double* out);
+/* Host-only (no GPU): the lowering of the two subset readers under the layout perm of the 2n index
+ * bits (logical -> physical, 2n entries; null: identity); rdm != 0: for the matrix.  Both readers
+ * evaluate out[o] = sum over b < 2^(n-k) of buf[G_out(o) | G_sum(b)], G(v) = the OR of the address
+ * generators (masks over the 2n physical positions) at the set bits of v.  out_gen (null: not
+ * returned): one generator per bit of the out index — marginal: k masks, both positions of
+ * qubits[j]; matrix: 2k single positions for o = a << k | a', [j] the column position of qubits[j]
+ * (bit j of a'), [k + j] its row position (bit j of a).  sum_gen (null: not returned): both
+ * positions of each of the n - k unlisted qubits, ascending.  info[0], [1] = elements of rho read
+ * (2^n or 2^(n+k)), low and high word; [2] = work-groups of the first kernel; [3] = kernel launches;
+ * [4] = scratch bytes of the partial sums; [5] = slices of the sum a work-group takes one of;
+ * [6] = generators that are bits of the thread index; [7] reserved (0).  The argument checks and
+ * error codes of the two readers; a perm that is no permutation or n_qubits outside
+ * [1, QSIM_DM_MAX_QUBITS] -> QSIM_ERR_INVALID_ARGUMENT. */
+int qsim_dm_marginal_plan(int n_qubits, const int32_t* qubits, int k, const int32_t* perm, int rdm,
+                          int32_t info[8], uint64_t* out_gen, uint64_t* sum_gen);
 
 /* ---- multi-GPU: state sharded by its high physical qubits, one process per GPU, RCCL ----
  * (the reference is single-GPU, README.md:361-367).  World size W = 2^g ranks;

@@ -98,6 +98,8 @@ _sig(hip, "qsim_apply_diagonal_layer", [_P, POINTER(c_double), c_uint64])
 _sig(hip, "qsim_apply_gate_raw", [_P, c_int, POINTER(qsim_gate), _P])
 _sig(hip, "qsim_plan_fused", [c_int, POINTER(qsim_gate), c_size_t, c_int, _P, _P,
                               POINTER(c_int32)])
+_sig(hip, "qsim_plan_stage_info", [c_int, POINTER(qsim_gate), c_size_t, c_int, _P, c_size_t, POINTER(c_size_t),
+                                   _P, c_size_t, POINTER(c_size_t), _P, c_size_t, POINTER(c_size_t)])
 _sig(hip, "qsim_set_jit", [c_int, c_int])
 _sig(hip, "qsim_jit_shutdown", [])
 _sig(hip, "qsim_set_relabel", [c_int, c_int])

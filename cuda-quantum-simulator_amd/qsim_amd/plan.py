@@ -23,6 +23,47 @@ def plan_fused(circuit: Circuit, hmax: int = 6):
     return order[:cnt], pass_of[:cnt], npass.value
 
 
+_STAGE_POS = ("first", "middle", "last", "only")
+_SWIZZLE = (None, "fixed", "searched")
+
+
+def plan_stage_info(circuit: Circuit, relayout: bool = False) -> dict:
+    """The stages of the plan run(circuit, Fused) would execute under the process settings in force
+    (qsim_plan_stage_info, host only; relayout: the relayout plan of a first run).  Returns
+    {"ops": [...], "passes": [...]}: one dict per executed tile op in execution order (src: source
+    gate index, -1 for the second and third op of a lowered SWAP; pass, stage, pos in first / middle
+    / last / only; kind, sub, p0, b0, b1, cmask, cm_reg, cm_thr, cm_out, d0_one) and one per pass
+    (single, h, r0, rb, hpos, hu_count, relayout, stages, ops, lds_fixed, lds_searched, swizzle: per
+    LDS round trip "fixed" or "searched", stage_bits: the register-bit mask of every stage)."""
+    arr, cnt = circuit.to_abi()
+    n = circuit.getNumQubits()
+    sizes = [ctypes.c_size_t(0) for _ in range(3)]
+
+    def call(bufs, caps):
+        args = []
+        for b, c, s in zip(bufs, caps, sizes):
+            args += [b.ctypes.data_as(ctypes.c_void_p) if b is not None else None, c, ctypes.byref(s)]
+        _lib.check(_lib.hip.qsim_plan_stage_info(n, arr, cnt, 1 if relayout else 0, *args))
+
+    call([None] * 3, [0] * 3)
+    caps = [s.value for s in sizes]
+    bufs = [np.zeros(max(1, c) * w, np.int32) for c, w in zip(caps, (16, 24, 8))]
+    call(bufs, caps)
+    ops_t, pass_t, stage_t = (b.reshape(-1, w)[:c].tolist() for b, c, w in zip(bufs, caps, (16, 24, 8)))
+    u32 = lambda x: x & 0xffffffff
+    ops = [{"src": r[0], "pass": r[1], "stage": r[2], "pos": _STAGE_POS[r[3]], "kind": r[4], "sub": r[5],
+            "p0": r[6], "b0": r[7], "b1": r[8], "cmask": u32(r[9]), "cm_reg": u32(r[10]), "cm_thr": u32(r[11]),
+            "cm_out": u32(r[12]) | (u32(r[13]) << 32), "d0_one": r[14]} for r in ops_t]
+    passes = [{"single": bool(r[0]), "h": r[1], "r0": r[2], "rb": r[3], "hu_count": r[4], "relayout": r[5],
+               "stages": r[6], "ops": r[7], "lds_fixed": r[8], "lds_searched": r[9], "hpos": r[11:11 + r[10]],
+               "swizzle": [], "stage_bits": []} for r in pass_t]
+    for r in stage_t:
+        passes[r[0]]["stage_bits"].append(u32(r[3]))
+        if r[5]:
+            passes[r[0]]["swizzle"].append(_SWIZZLE[r[5]])
+    return {"ops": ops, "passes": passes}
+
+
 def set_jit(mode: int = -1, min_qubits: int = -1) -> None:
     """Circuit-specialised pass kernels: mode 0 off, 1 background compile (default), 2 compile
     on a plan's first run; states below `min_qubits` use the pass interpreter (qsim_set_jit)."""

@@ -136,6 +136,30 @@ int qsim_apply_diagonal_layer(qsim_state* s, const double* gate_params, uint64_t
  * gates on disjoint qubits. */
 int qsim_plan_fused(int n_qubits, const qsim_gate* gates, size_t count, int hmax,
                     int32_t* order, int32_t* pass_of, int32_t* n_passes);
+/* Host-only, read-only: the stages of the plan a fused qsim_run of this gate list would execute on
+ * a state of n_qubits under the process settings in force (tile height, stage width, tile-constant
+ * controls, QSIM_TILE_R0 and the planner pins), read out of that plan; relayout != 0: the relayout
+ * plan of a first run instead (QSIM_ERR_RUNTIME when none exists).  Three tables of int32 records;
+ * each is filled up to its capacity in records (the buffer may be null) and its full count is
+ * returned, so a caller may ask for the counts first.
+ *   ops, 16 per executed tile op, in execution order (a gate run per-gate gives one record too):
+ *     0 source gate index (-1: the second and third controlled-X of a lowered SWAP), 1 pass,
+ *     2 stage within the pass (-1: unstaged tile or per-gate), 3 stage position (0 first: straight
+ *     from the HBM loads, 1 middle: LDS on both sides, 2 last: straight into the stores, 3 only),
+ *     4 kind (0 2x2, 1 diagonal, 2 SWAP), 5 sub-kind as the kernel dispatches it (an H beyond the
+ *     pass's unnormalised-butterfly cap is relabelled general), 6 p0 (register bit of the target,
+ *     -1: a thread bit), 7 b0 and 8 b1 (tile bits of the targets; qubits for a per-gate op),
+ *     9 controls inside the tile (tile bits), 10 cm_reg (those on register bits, register space),
+ *     11 cm_thr (those on thread bits, tile space), 12 / 13 low / high word of cm_out (controls
+ *     outside the tile, physical positions), 14 d0_one, 15 zero.
+ *   passes, 24 per pass: 0 single (per-gate fallback), 1 h, 2 r0, 3 rb (0: unstaged), 4 hu_count,
+ *     5 relayout, 6 stages, 7 op records, 8 / 9 LDS round trips under the fixed / a searched
+ *     swizzle, 10 tile bits above the run, 11.. their physical positions (hpos).
+ *   stages, 8 per stage: 0 pass, 1 stage, 2 position (as above), 3 register-bit mask (tile bits),
+ *     4 ops, 5 the LDS round trip after it (0 none, 1 fixed swizzle, 2 searched), 6 tscatter, 7 zero. */
+int qsim_plan_stage_info(int n_qubits, const qsim_gate* gates, size_t count, int relayout, int32_t* ops,
+                         size_t op_cap, size_t* n_ops, int32_t* passes, size_t pass_cap, size_t* n_passes,
+                         int32_t* stages, size_t stage_cap, size_t* n_stages);
 /* Circuit-specialised pass kernels (hipRTC, no reference counterpart: the reference launches one
  * fixed kernel per gate, src/Simulator.cu:38-154).  mode 0 = off, 1 = compile in the background
  * on a plan's first run and switch to the compiled kernels when ready (default), 2 = compile on

@@ -93,8 +93,14 @@ static void dm_channel(std::vector<Op>& out, int n, int type, int q, double p) {
     }
 }
 
+// tags (introspection, may be null): one entry per op pushed, the gate it follows and where it came
+// from (the origin word of qsim_dm_plan_stage_info).
 void dm_lower(int n, const qsim_gate* gates, size_t count, const qsim_noise_channel* ch,
-              size_t nch, std::vector<Op>& out, bool reference_y) {
+              size_t nch, std::vector<Op>& out, bool reference_y, std::vector<StageInfoTag>* tags) {
+    auto tag = [&](size_t gate, int origin, int qubit) {  // the ops pushed since the last call
+        for (int seq = 0; tags && tags->size() < out.size(); ++seq)
+            tags->push_back(StageInfoTag{(int32_t)gate, origin | (qubit << 8) | (seq << 16)});
+    };
     for (size_t c = 0; c < nch; ++c) {
         if (ch[c].type < 0 || ch[c].type > 5) fail(QSIM_ERR_INVALID_ARGUMENT, "unknown noise type");
         if (ch[c].qubit < -1 || ch[c].qubit >= n)
@@ -107,7 +113,9 @@ void dm_lower(int n, const qsim_gate* gates, size_t count, const qsim_noise_chan
         Op o = lower_gate(g, n);
         o.src = (int)i;
         out.push_back(dm_row(o, n));
+        tag(i, QSIM_DM_ORIGIN_ROW, g.qubits[g.nqubits - 1]);
         out.push_back(dm_col(o));
+        tag(i, QSIM_DM_ORIGIN_COL, g.qubits[g.nqubits - 1]);
         if (reference_y && g.type == QSIM_GATE_Y) {  // dmApplyY's extra sign (-Y rho Y^dag)
             Op neg;
             neg.kind = K_DIAG;
@@ -117,11 +125,14 @@ void dm_lower(int n, const qsim_gate* gates, size_t count, const qsim_noise_chan
             neg.m[0] = neg.m[2] = -1.0;
             neg.src = (int)i;
             out.push_back(neg);
+            tag(i, QSIM_DM_ORIGIN_SIGN, 0);
         }
         for (int k = 0; k < g.nqubits; ++k)
             for (size_t c = 0; c < nch; ++c)
-                if (ch[c].qubit < 0 || ch[c].qubit == g.qubits[k])
+                if (ch[c].qubit < 0 || ch[c].qubit == g.qubits[k]) {
                     dm_channel(out, n, ch[c].type, g.qubits[k], ch[c].probability);
+                    tag(i, QSIM_DM_ORIGIN_CHANNEL + ch[c].type, g.qubits[k]);
+                }
     }
 }
 
@@ -228,12 +239,28 @@ static LayoutChoice dm_choose_layout(int nbits, const std::vector<Op>& ops, size
 }
 // The checks and the lowering that the host-only entries below start with.
 static std::vector<Op> dm_lower_checked(int n, const qsim_gate* gates, size_t count, const qsim_noise_channel* channels,
-                                        size_t n_channels, int flags) {
+                                        size_t n_channels, int flags, std::vector<StageInfoTag>* tags = nullptr) {
+    if (n < 1 || n > QSIM_DM_MAX_QUBITS) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
     QSIM_REQUIRE(gates || count == 0, QSIM_ERR_INVALID_ARGUMENT, "null gate list");
     QSIM_REQUIRE(channels || n_channels == 0, QSIM_ERR_INVALID_ARGUMENT, "null channel list");
     std::vector<Op> ops;
-    dm_lower(n, gates, count, channels, n_channels, ops, (flags & QSIM_DM_REFERENCE_Y) != 0);
+    dm_lower(n, gates, count, channels, n_channels, ops, (flags & QSIM_DM_REFERENCE_Y) != 0, tags);
     return ops;
+}
+// The plan qsim_dm_run's fused path executes for these ops when the state lies under the labels
+// `perm` of the 2n index bits (logical -> physical; null: the identity).  pi: the labels checked.
+static Plan dm_plan_under(int n, std::vector<Op>& ops, const int32_t* perm, std::vector<int>& pi) {
+    pi.resize(2 * n);
+    for (int b = 0; b < 2 * n; ++b) pi[b] = perm ? perm[b] : b;
+    std::vector<int> chk(pi);
+    std::sort(chk.begin(), chk.end());
+    for (int b = 0; b < 2 * n; ++b)
+        if (chk[b] != b) fail(QSIM_ERR_INVALID_ARGUMENT, "perm is not a permutation");
+    if (perm)
+        for (Op& o : ops) o = permute_op(o, pi);
+    const int th = tile_height_for(2 * n);
+    const TileHeightScope tile_h(th, tile_rb_for(2 * n, th));
+    return plan_fused(ops, 2 * n);
 }
 }  // namespace qsim_hip
 
@@ -317,7 +344,6 @@ int qsim_dm_run(qsim_state* s, int n, const qsim_gate* gates, size_t count,
 int qsim_dm_plan_info(int n, const qsim_gate* gates, size_t count, const qsim_noise_channel* channels,
                       size_t n_channels, int flags, int32_t* info, size_t cap, size_t* n_passes) {
     return guarded([&] {
-        if (n < 1 || n > QSIM_DM_MAX_QUBITS) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
         const std::vector<Op> ops = dm_lower_checked(n, gates, count, channels, n_channels, flags);
         const int th = tile_height_for(2 * n);
         const TileHeightScope tile_h(th, tile_rb_for(2 * n, th));
@@ -363,11 +389,38 @@ int qsim_dm_plan_info(int n, const qsim_gate* gates, size_t count, const qsim_no
 int qsim_dm_jit_source(int n, const qsim_gate* gates, size_t count, const qsim_noise_channel* channels,
                        size_t n_channels, int flags, char* buf, size_t cap, size_t* len) {
     return guarded([&] {
-        if (n < 1 || n > QSIM_DM_MAX_QUBITS) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
         const std::vector<Op> ops = dm_lower_checked(n, gates, count, channels, n_channels, flags);
         const int th = tile_height_for(2 * n);
         const TileHeightScope tile_h(th, tile_rb_for(2 * n, th));
         copy_source(jit_source(plan_fused(ops, 2 * n)), buf, cap, len);
+    });
+}
+
+int qsim_dm_plan_stage_info(int n, const qsim_gate* gates, size_t count, const qsim_noise_channel* channels,
+                            size_t n_channels, int flags, const int32_t* perm, int32_t* ops, size_t op_cap,
+                            size_t* n_ops, int32_t* passes, size_t pass_cap, size_t* n_passes, int32_t* stages,
+                            size_t stage_cap, size_t* n_stages) {
+    return guarded([&] {
+        std::vector<StageInfoTag> tags;
+        std::vector<Op> lowered = dm_lower_checked(n, gates, count, channels, n_channels, flags, &tags);
+        // (an op's src is read by nothing but the Pauli-frame arms: here it names the lowered op)
+        for (size_t k = 0; k < lowered.size(); ++k) lowered[k].src = (int)k;
+        std::vector<int> pi;
+        const Plan plan = dm_plan_under(n, lowered, perm, pi);
+        write_stage_info(plan, &tags, ops, op_cap, n_ops, passes, pass_cap, n_passes, stages, stage_cap, n_stages);
+    });
+}
+
+int qsim_dm_plan_exec_host(int n, const qsim_gate* gates, size_t count, const qsim_noise_channel* channels,
+                           size_t n_channels, int flags, const int32_t* perm, double* amps, int* passes) {
+    return guarded([&] {
+        QSIM_REQUIRE(amps, QSIM_ERR_INVALID_ARGUMENT, "null amplitudes");
+        std::vector<Op> lowered = dm_lower_checked(n, gates, count, channels, n_channels, flags);
+        if (2 * n < 10 || 2 * n > 26) fail(QSIM_ERR_INVALID_ARGUMENT, "host execution: 10..26 index bits");
+        std::vector<int> pi;
+        const Plan plan = dm_plan_under(n, lowered, perm, pi);
+        exec_plan_on_host(plan, 2 * n, amps, perm ? pi.data() : nullptr);
+        if (passes) *passes = (int)plan.passes.size();
     });
 }
 

@@ -206,6 +206,18 @@ constexpr int kTileR0 = 6;    // contiguous run bits of a staged tile (QSIM_TILE
 // avoid_first: the same for the plan's FIRST pass only (the sharded engine: the pivots of the
 // remap before a step steer its leading pass, those of the remap after it every pass).
 Plan plan_fused(const std::vector<Op>& ops, int n, int hmax = -1, uint64_t avoid = 0, uint64_t avoid_first = 0);
+// Host-only introspection of a plan (tests).  write_stage_info (capi.hip): the record tables of
+// qsim_plan_stage_info; tags (may be null) replaces an op's source index by (gate, origin word).
+// exec_plan_on_host (relayout.hip): the plan's staged passes executed on 2^n interleaved re/im
+// amplitudes with the kernels' index math (QSIM_ERR_RUNTIME on any other pass); amps is in logical
+// order under the labels pi (bit b -> position pi[b]; null: the identity) the plan was made for.
+struct StageInfoTag {
+    int32_t gate, origin;
+};
+void write_stage_info(const Plan& plan, const std::vector<StageInfoTag>* tags, int32_t* ops, size_t op_cap,
+                      size_t* n_ops, int32_t* passes, size_t pass_cap, size_t* n_passes, int32_t* stages,
+                      size_t stage_cap, size_t* n_stages);
+void exec_plan_on_host(const Plan& plan, int n, double* amps, const int* pi = nullptr);
 // Rebuild the last pass of `plan` (staged) as a relayout pass that stores load position p at
 // tau[p] (a permutation of 0..n-1; the sharded engine's fused remap pack / unpack).
 void relayout_last_pass(Plan& plan, int n, const int* tau);
@@ -488,7 +500,8 @@ void launch_pull_gate(const double2* src, double2* dst, int n, uint64_t batch, c
 
 // Density matrices as 2n-index-bit states (density.hip).
 void dm_lower(int n, const qsim_gate* gates, size_t count, const qsim_noise_channel* ch,
-              size_t nch, std::vector<Op>& out, bool reference_y = false);
+              size_t nch, std::vector<Op>& out, bool reference_y = false,
+              std::vector<StageInfoTag>* tags = nullptr);
 void dm_lower_channel(int n, int type, int qubit, double p, std::vector<Op>& out);
 void launch_dm_diag(const double2* rho, int n, double* out, hipStream_t s);
 void launch_dm_init(double2* rho, const double2* psi, int n, hipStream_t s);

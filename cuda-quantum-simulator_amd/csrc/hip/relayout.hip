@@ -714,7 +714,14 @@ void exec_stage_op(const TileOp& op, cd* v, int R, uint32_t jb) {
     const uint32_t cr = op.cm_reg, ct = op.cm_thr;
     const bool thr_ok = (jb & ct) == ct;
     if (op.kind == K_DIAG) {
-        const cd d0(op.m[0], op.m[1]), d1(op.m[2], op.m[3]);
+        // the |1>-side phase by sub-kind, as the kernels dispatch it (device_ops.hpp diag1): a
+        // lowering that leaves sub and matrix in disagreement shows here as it would on the device
+        const cd d0(op.m[0], op.m[1]);
+        const cd d1 = op.sub == S_I     ? cd(0.0, 1.0)
+                      : op.sub == S_MI  ? cd(0.0, -1.0)
+                      : op.sub == S_T   ? cd(kInvSqrt2, kInvSqrt2)
+                      : op.sub == S_TDG ? cd(kInvSqrt2, -kInvSqrt2)
+                                        : cd(op.m[2], op.m[3]);
         const bool tbit = ((jb >> op.b0) & 1u) != 0;
         for (int r = 0; r < R; ++r) {
             const bool bit = op.p0 >= 0 ? (((r >> op.p0) & 1) != 0) : tbit;
@@ -826,6 +833,25 @@ void exec_plan_host(const Plan& plan, int n, std::vector<cd>& st, size_t first =
 }
 }  // namespace
 
+void exec_plan_on_host(const Plan& plan, int n, double* amps, const int* pi) {
+    const uint64_t N = 1ull << n;
+    auto phys = [&](uint64_t i) {  // logical index -> physical under pi
+        if (!pi) return i;
+        uint64_t k = 0;
+        for (int b = 0; b < n; ++b)
+            if ((i >> b) & 1ull) k |= 1ull << pi[b];
+        return k;
+    };
+    std::vector<cd> st(N);
+    for (uint64_t i = 0; i < N; ++i) st[phys(i)] = cd(amps[2 * i], amps[2 * i + 1]);
+    exec_plan_host(plan, n, st);
+    for (uint64_t i = 0; i < N; ++i) {
+        const cd a = st[phys(i)];
+        amps[2 * i] = a.real();
+        amps[2 * i + 1] = a.imag();
+    }
+}
+
 }  // namespace qsim_hip
 
 extern "C" int qsim_plan_exec_host(int n_qubits, const qsim_gate* gates, size_t count, int mode, double* amps,
@@ -847,14 +873,7 @@ extern "C" int qsim_plan_exec_host(int n_qubits, const qsim_gate* gates, size_t 
             for (int q = 0; q < n; ++q)
                 if (chk[q] != q) fail(QSIM_ERR_INVALID_ARGUMENT, "perm is not a permutation");
             plan = plan_permutation_pass(n, from);
-            const uint64_t N = 1ull << n;
-            std::vector<std::complex<double>> st(N);
-            for (uint64_t i = 0; i < N; ++i) st[i] = std::complex<double>(amps[2 * i], amps[2 * i + 1]);
-            exec_plan_host(plan, n, st);
-            for (uint64_t i = 0; i < N; ++i) {
-                amps[2 * i] = st[i].real();
-                amps[2 * i + 1] = st[i].imag();
-            }
+            exec_plan_on_host(plan, n, amps);
             if (passes) *passes = (int)plan.passes.size();
             return;
         }
@@ -867,22 +886,7 @@ extern "C" int qsim_plan_exec_host(int n_qubits, const qsim_gate* gates, size_t 
             const TileHeightScope scope(6);
             plan = plan_fused(lower(pi), n, 6);
         }
-        const uint64_t N = 1ull << n;
-        std::vector<std::complex<double>> st(N);
-        for (uint64_t i = 0; i < N; ++i) {  // logical index -> physical under pi
-            uint64_t k = 0;
-            for (int q = 0; q < n; ++q)
-                if ((i >> q) & 1ull) k |= 1ull << pi[q];
-            st[k] = std::complex<double>(amps[2 * i], amps[2 * i + 1]);
-        }
-        exec_plan_host(plan, n, st);
-        for (uint64_t i = 0; i < N; ++i) {
-            uint64_t k = 0;
-            for (int q = 0; q < n; ++q)
-                if ((i >> q) & 1ull) k |= 1ull << pi[q];
-            amps[2 * i] = st[k].real();
-            amps[2 * i + 1] = st[k].imag();
-        }
+        exec_plan_on_host(plan, n, amps, pi.data());
         if (perm)
             for (int q = 0; q < n; ++q) perm[q] = pi[q];
         if (passes) *passes = (int)plan.passes.size();

@@ -200,6 +200,11 @@ _sig(hip, "qsim_dm_plan_info", [c_int, POINTER(qsim_gate), c_size_t, POINTER(qsi
                                   c_int, POINTER(c_int32), c_size_t, POINTER(c_size_t)])
 _sig(hip, "qsim_dm_jit_source", [c_int, POINTER(qsim_gate), c_size_t, POINTER(qsim_noise_channel), c_size_t,
                                    c_int, c_char_p, c_size_t, POINTER(c_size_t)])
+_sig(hip, "qsim_dm_plan_stage_info", [c_int, POINTER(qsim_gate), c_size_t, POINTER(qsim_noise_channel), c_size_t,
+                                      c_int, POINTER(c_int32), _P, c_size_t, POINTER(c_size_t), _P, c_size_t,
+                                      POINTER(c_size_t), _P, c_size_t, POINTER(c_size_t)])
+_sig(hip, "qsim_dm_plan_exec_host", [c_int, POINTER(qsim_gate), c_size_t, POINTER(qsim_noise_channel), c_size_t,
+                                     c_int, POINTER(c_int32), _P, POINTER(c_int)])
 _sig(hip, "qsim_dm_run", [_P, c_int, POINTER(qsim_gate), c_size_t, POINTER(qsim_noise_channel),
                           c_size_t, c_int])
 _sig(hip, "qsim_dm_apply_channel", [_P, c_int, c_int, c_int, c_double])

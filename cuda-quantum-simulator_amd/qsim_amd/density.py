@@ -149,6 +149,7 @@ class DensityMatrixSimulator:
         return self._rho
 
     def setSeed(self, seed: int) -> None: self._rng = np.random.default_rng(seed)
+    def setNoiseModel(self, nm: NoiseModel) -> None: self._noise = nm
 
     def setReferenceCompatible(self, on: bool = True) -> None:
         """Y as the reference's dmApplyY (-Y rho Y^dag, src/DensityMatrix.cu:507-546)."""

@@ -37,13 +37,19 @@ def plan_stage_info(circuit: Circuit, relayout: bool = False) -> dict:
     LDS round trip "fixed" or "searched", stage_bits: the register-bit mask of every stage)."""
     arr, cnt = circuit.to_abi()
     n = circuit.getNumQubits()
+    return _stage_info(lambda *args: _lib.hip.qsim_plan_stage_info(n, arr, cnt, 1 if relayout else 0, *args))
+
+
+def _stage_info(entry) -> dict:
+    """The three record tables of qsim_plan_stage_info / qsim_dm_plan_stage_info as dicts; entry
+    takes the nine table arguments (buffer, capacity, count of each)."""
     sizes = [ctypes.c_size_t(0) for _ in range(3)]
 
     def call(bufs, caps):
         args = []
         for b, c, s in zip(bufs, caps, sizes):
             args += [b.ctypes.data_as(ctypes.c_void_p) if b is not None else None, c, ctypes.byref(s)]
-        _lib.check(_lib.hip.qsim_plan_stage_info(n, arr, cnt, 1 if relayout else 0, *args))
+        _lib.check(entry(*args))
 
     call([None] * 3, [0] * 3)
     caps = [s.value for s in sizes]
@@ -53,7 +59,7 @@ def plan_stage_info(circuit: Circuit, relayout: bool = False) -> dict:
     u32 = lambda x: x & 0xffffffff
     ops = [{"src": r[0], "pass": r[1], "stage": r[2], "pos": _STAGE_POS[r[3]], "kind": r[4], "sub": r[5],
             "p0": r[6], "b0": r[7], "b1": r[8], "cmask": u32(r[9]), "cm_reg": u32(r[10]), "cm_thr": u32(r[11]),
-            "cm_out": u32(r[12]) | (u32(r[13]) << 32), "d0_one": r[14]} for r in ops_t]
+            "cm_out": u32(r[12]) | (u32(r[13]) << 32), "d0_one": r[14], "origin": r[15]} for r in ops_t]
     passes = [{"single": bool(r[0]), "h": r[1], "r0": r[2], "rb": r[3], "hu_count": r[4], "relayout": r[5],
                "stages": r[6], "ops": r[7], "lds_fixed": r[8], "lds_searched": r[9], "hpos": r[11:11 + r[10]],
                "swizzle": [], "stage_bits": []} for r in pass_t]
@@ -62,6 +68,50 @@ def plan_stage_info(circuit: Circuit, relayout: bool = False) -> dict:
         if r[5]:
             passes[r[0]]["swizzle"].append(_SWIZZLE[r[5]])
     return {"ops": ops, "passes": passes}
+
+
+_DM_ORIGINS = ("", "row", "col", "sign", "ch0", "ch1", "ch2", "ch3", "ch4", "ch5")
+
+
+def _dm_args(n: int, circuit: Circuit, channels, perm):
+    arr, cnt = circuit.to_abi()
+    ch = (_lib.qsim_noise_channel * max(1, len(channels)))()
+    for i, (t, q, p) in enumerate(channels):
+        ch[i].type, ch[i].qubit, ch[i].probability = int(t), int(q), float(p)
+    return arr, cnt, ch, len(channels), _perm_arg(2 * n, perm)
+
+
+def dm_plan_stage_info(circuit: Circuit, channels=(), flags: int = 1, perm=None) -> dict:
+    """plan_stage_info of the plan DensityMatrixSimulator.run executes for (circuit, channels as
+    (type, qubit or -1, p), flags) on a state under the labels perm of the 2n index bits (logical ->
+    physical, StateVector.perm() of the density matrix's state; None: identity), host only
+    (qsim_dm_plan_stage_info).  Every op record also names where it came from: src is the gate it
+    belongs to or follows, origin "row" / "col" (the gate and its conjugate), "sign" (the -1 of the
+    reference's Y), "ch0".."ch5" (a channel of that noise type) or "" (the second and third op of a
+    lowered SWAP); qubit: the gate's target or the channel's qubit; seq: the op's place in its
+    channel's sequence."""
+    n = circuit.getNumQubits()
+    arr, cnt, ch, nch, pi = _dm_args(n, circuit, channels, perm)
+    info = _stage_info(lambda *args: _lib.hip.qsim_dm_plan_stage_info(n, arr, cnt, ch, nch, flags, pi, *args))
+    for r in info["ops"]:
+        word = r["origin"]
+        r["origin"], r["qubit"], r["seq"] = _DM_ORIGINS[word & 0xff], (word >> 8) & 0xff, (word >> 16) & 0xff
+    return info
+
+
+def dm_plan_exec_host(circuit: Circuit, rho, channels=(), flags: int = 1, perm=None):
+    """That plan executed on the host with the staged kernels' index math on the 2^n x 2^n matrix
+    rho (qsim_dm_plan_exec_host; 10..26 index bits, staged passes only; no GPU).  Returns (rho after
+    the run, pass count)."""
+    n = circuit.getNumQubits()
+    arr, cnt, ch, nch, pi = _dm_args(n, circuit, channels, perm)
+    st = np.array(rho, dtype=np.complex128).reshape(-1)
+    if st.shape != (1 << (2 * n),):
+        raise ValueError("rho must hold 4^n elements")
+    passes = ctypes.c_int(0)
+    _lib.check(_lib.hip.qsim_dm_plan_exec_host(n, arr, cnt, ch, nch, flags, pi, st.ctypes.data_as(ctypes.c_void_p),
+                                               ctypes.byref(passes)))
+    return st.reshape(1 << n, 1 << n), passes.value
 
 
 def set_jit(mode: int = -1, min_qubits: int = -1) -> None:

@@ -151,7 +151,7 @@ int qsim_plan_fused(int n_qubits, const qsim_gate* gates, size_t count, int hmax
  *     -1: a thread bit), 7 b0 and 8 b1 (tile bits of the targets; qubits for a per-gate op),
  *     9 controls inside the tile (tile bits), 10 cm_reg (those on register bits, register space),
  *     11 cm_thr (those on thread bits, tile space), 12 / 13 low / high word of cm_out (controls
- *     outside the tile, physical positions), 14 d0_one, 15 zero.
+ *     outside the tile, physical positions), 14 d0_one, 15 zero (qsim_dm_plan_stage_info: origin).
  *   passes, 24 per pass: 0 single (per-gate fallback), 1 h, 2 r0, 3 rb (0: unstaged), 4 hu_count,
  *     5 relayout, 6 stages, 7 op records, 8 / 9 LDS round trips under the fixed / a searched
  *     swizzle, 10 tile bits above the run, 11.. their physical positions (hpos).
@@ -587,6 +587,29 @@ int qsim_dm_plan_info(int n_qubits, const qsim_gate* gates, size_t count, const 
 /* Host-only: the circuit-specialised kernel source of that plan (as qsim_jit_source). */
 int qsim_dm_jit_source(int n_qubits, const qsim_gate* gates, size_t count, const qsim_noise_channel* channels,
                        size_t n_channels, int flags, char* buf, size_t cap, size_t* len);
+/* Host-only: the records of qsim_plan_stage_info for the plan qsim_dm_run (QSIM_RUN_FUSED) executes
+ * for (n_qubits, gates, channels, flags) on a state that lies under the labels perm of the 2n index
+ * bits (logical -> physical, column bit q, row bit q + n; null: the identity; qsim_state_perm of
+ * the state): the lowered ops moved through perm, planned at the height and stage width of 2n index
+ * bits.  Field 0 of an op record is the gate the op belongs to (a channel op: the gate it follows),
+ * field 15 its origin: bits 0-7 QSIM_DM_ORIGIN_ROW (the gate on the row bits), _COL (its conjugate on
+ * the column bits), _SIGN (the -1 of QSIM_DM_REFERENCE_Y) or _CHANNEL + noise type; bits 8-15 the
+ * qubit (a gate: its target); bits 16-23 the op's place in its channel's sequence.  0 for the second
+ * and third controlled-X of a lowered SWAP. */
+#define QSIM_DM_ORIGIN_ROW 1
+#define QSIM_DM_ORIGIN_COL 2
+#define QSIM_DM_ORIGIN_SIGN 3
+#define QSIM_DM_ORIGIN_CHANNEL 4
+int qsim_dm_plan_stage_info(int n_qubits, const qsim_gate* gates, size_t count, const qsim_noise_channel* channels,
+                            size_t n_channels, int flags, const int32_t* perm, int32_t* ops, size_t op_cap,
+                            size_t* n_ops, int32_t* passes, size_t pass_cap, size_t* n_passes, int32_t* stages,
+                            size_t stage_cap, size_t* n_stages);
+/* Host-only: that plan executed on the host as qsim_plan_exec_host executes one (tests of the
+ * lowering and of the planners' index math for its ops; no GPU).  amps: 4^n interleaved re/im,
+ * rho row-major (logical order), updated in place; 10..26 index bits (n = 5..13), staged passes only
+ * (QSIM_ERR_RUNTIME on a per-gate step or an unstaged tile).  passes: the plan's pass count. */
+int qsim_dm_plan_exec_host(int n_qubits, const qsim_gate* gates, size_t count, const qsim_noise_channel* channels,
+                           size_t n_channels, int flags, const int32_t* perm, double* amps, int* passes);
 /* One channel (applyDepolarizing ... applyBitPhaseFlip, :298-356) on `qubit`. */
 int qsim_dm_apply_channel(qsim_state* rho, int n_qubits, int type, int qubit, double p);
 int qsim_dm_diagonal(qsim_state* rho, int n_qubits, double* dst);          /* 2^n: Re rho_ii */

@@ -17,8 +17,9 @@ tests/test_fused_matrix_gpu.py and the child script tests/fused_child.py.
   * `check`: bit-identity outside the may-change mask, tolerance 0 for circuits of exact ops, the
     project's 1e-12 per component otherwise.
 
-Out of scope here, each with oracle tests of its own: the Pauli-frame arms (FR = true, batched
-noisy runs), sub-space launches (fix_mask, the sharded engine) and the density-matrix passes.
+Out of scope here: the Pauli-frame arms (FR = true, batched noisy runs) and sub-space launches
+(fix_mask, the sharded engine), each with oracle tests of its own, and the density-matrix passes,
+which have this module's counterpart in tests/dm_pass_cases.py.
 """
 import math
 

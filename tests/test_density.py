@@ -88,6 +88,8 @@ def test_large_fused_equals_per_gate(qsim, gpu_ready):
     b.run(c)
     np.testing.assert_allclose(a.getProbabilities(), b.getProbabilities(), atol=1e-12, rtol=0)
     assert abs(a.getTrace() - 1.0) < 1e-10
+    # the two 22-bit states in full, off-diagonal elements included, compared on the device
+    assert a.density.state.maxAbsDiff(b.density.state) <= 1e-12
 
 
 @pytest.mark.gpu

@@ -252,6 +252,9 @@ struct qsim_batch {
     DevBuf ops, stages;             // fused-plan descriptors
     DevBuf cliff;                   // per-step Clifford codes of the current run (frame build)
     DevBuf expect_terms;            // term table of the last expectation value (expect.hip)
+    // coefficient table of the last parameter sweep (qsim_batch_run_sweep): [slot][member][8]
+    // doubles, grown on demand like d_frames
+    DevBuf sweep_table;
     PlanCache plans;
     Timer timer;
     Scratch scratch, scratch2;
@@ -528,9 +531,152 @@ void canonicalize(qsim_batch* b) {
     launch_fused(b->d, n, (uint64_t)b->batch, pe.plan, (const TileOp*)b->ops.ptr, (const Stage*)b->stages.ptr,
                  b->stream, &b->timer);
 }
+// ---- parameter sweeps (qsim_batch_run_sweep / qsim_batch_sweep_plan) ----
+// The checks both entries share.  Returns the gate list with every parameterised gate's angle
+// replaced by the placeholder — what is validated, planned and keyed, so neither the plan nor the
+// qubit layout depends on the members' angles — and the slots (gate indices, list order).
+std::vector<qsim_gate> sweep_arguments(int n, const qsim_gate* gates, size_t count, int flags,
+                                       std::vector<size_t>& slots) {
+    if (!gates && count) fail(QSIM_ERR_INVALID_ARGUMENT, "null gate list");
+    if (flags & ~QSIM_BATCH_PER_GATE)
+        fail(QSIM_ERR_INVALID_ARGUMENT, "a parameter sweep takes flags 0 or QSIM_BATCH_PER_GATE");
+    std::vector<qsim_gate> pg(gates, gates + count);
+    slots.clear();
+    for (size_t i = 0; i < count; ++i) {
+        if (gate_is_parameterised(pg[i].type)) {
+            pg[i].parameter = kSweepPlaceholderAngle;
+            slots.push_back(i);
+        }
+        validate_gate(pg[i], n);
+    }
+    return pg;
+}
+bool sweep_fused_path(int n, int flags) {
+    return n >= 10 && env_switch("QSIM_BATCH_FUSED", true) && !(flags & QSIM_BATCH_PER_GATE);
+}
+// The placeholder list lowered under `perm`; a parameterised gate's op carries its slot in src.
+std::vector<Op> sweep_lower(int n, const std::vector<qsim_gate>& pg, const std::vector<int>& perm, bool slots) {
+    std::vector<Op> ops = lower_gates(n, pg.data(), pg.size(), perm);
+    int k = 0;
+    for (size_t i = 0; i < ops.size(); ++i) ops[i].src = slots && gate_is_parameterised(pg[i].type) ? k++ : -1;
+    return ops;
+}
 }  // namespace
 
 extern "C" {
+
+int qsim_batch_run_sweep(qsim_batch* b, const qsim_gate* gates, size_t count, const double* angles,
+                         size_t n_slots, int flags) {
+    bool plain = false;  // no parameterised gate: qsim_batch_run without channels
+    const int rc = guarded([&] {
+        need(b);
+        std::vector<size_t> slots;
+        const std::vector<qsim_gate> pg = sweep_arguments(b->n, gates, count, flags, slots);
+        const size_t P = slots.size();
+        if (n_slots != P) fail(QSIM_ERR_INVALID_ARGUMENT, "n_slots must be the number of parameterised gates");
+        if (P && !angles) fail(QSIM_ERR_INVALID_ARGUMENT, "null angles");
+        if (count == 0) return;
+        if (P == 0) {
+            plain = true;
+            return;
+        }
+        // the table first: a bad angle or a failed allocation leaves the states as they are
+        const size_t B = (size_t)b->batch;
+        std::vector<double> tab(8 * B * P);
+        for (size_t k = 0; k < P; ++k) {
+            qsim_gate g = pg[slots[k]];
+            for (size_t t = 0; t < B; ++t) {
+                g.parameter = angles[t * P + k];
+                const Op op = lower_gate(g, b->n);  // (one definition of each rotation)
+                std::memcpy(&tab[8 * (k * B + t)], op.m, sizeof(op.m));
+            }
+        }
+        try {
+            b->sweep_table.upload(tab.data(), tab.size() * sizeof(double), b->stream);
+        } catch (...) {  // (a refused growth left no block behind)
+            if (!b->sweep_table.ptr) {
+                b->sweep_table.cap = 0;
+                b->sweep_table.shadow.clear();
+            }
+            throw;
+        }
+        const double* d_tab = (const double*)b->sweep_table.ptr;
+        materialize(b);  // a sweep is noise-free: carried Pauli frames are applied first
+        const bool fused_path = sweep_fused_path(b->n, flags);
+        if (fused_path && b->basis && b->perm.empty()) {
+            // first fused run of |0..0> members: the layout qsim_batch_run would choose for the
+            // placeholder circuit (the same rule, memoised under the same kind)
+            int eff = b->n;
+            while ((1ll << (eff - b->n)) < (long long)b->batch) ++eff;
+            if (relabel_enabled(eff)) {
+                auto lower_under = [&](const std::vector<int>& pi) { return sweep_lower(b->n, pg, pi, false); };
+                const CtrlOutOff ctrl_off;
+                if (!layout_memo_get(b->n, 1, pg.data(), count * sizeof(qsim_gate), b->perm)) {
+                    b->perm = choose_layout(b->n, lower_under, relabel_tries()).perm;
+                    layout_memo_put(b->n, 1, pg.data(), count * sizeof(qsim_gate), b->perm);
+                }
+            }
+        }
+        b->basis = false;
+        const std::vector<Op> ops = sweep_lower(b->n, pg, b->perm, true);
+        if (!fused_path) {  // one launch per gate over all members (batch_sweep.hip for the slots)
+            for (const Op& op : ops) {
+                if (op.src >= 0) launch_sweep_op(b->d, b->n, B, op, d_tab + 8 * B * (size_t)op.src, b->stream, &b->timer);
+                else launch_op(b->d, b->n, B, op, b->stream, &b->timer);
+            }
+            return;
+        }
+        const CtrlOutOff ctrl_off;  // (every control is a tile bit, as in the Pauli-frame passes)
+        PlanCache::Entry& pe = b->plans.get(ops, b->n, b->stream);
+        const Plan& plan = pe.plan;
+        // circuit-specialised kernels only for the passes without a member-dependent op
+        std::vector<char> tabled(plan.passes.size());
+        bool any_plain = false;
+        for (size_t p = 0; p < plan.passes.size(); ++p) {
+            tabled[p] = pass_has_step_op(plan, p);
+            any_plain = any_plain || !tabled[p];
+        }
+        int eff = b->n;
+        while ((1ll << (eff - b->n)) < (long long)b->batch) ++eff;
+        const JitModule* jm = any_plain ? jit_for(pe.jit, plan, eff) : nullptr;
+        b->ops.upload(plan.ops.data(), plan.ops.size() * sizeof(TileOp), b->stream);
+        b->stages.upload(plan.stages.data(), plan.stages.size() * sizeof(Stage), b->stream);
+        launch_fused(b->d, b->n, B, plan, (const TileOp*)b->ops.ptr, (const Stage*)b->stages.ptr, b->stream,
+                     &b->timer, jm, nullptr, FusedRange(), d_tab);
+        b->last_passes = (int)plan.passes.size();
+        b->last_jit_passes = 0;
+        if (jm)
+            for (size_t p = 0; p < jm->fn.size() && p < tabled.size(); ++p)
+                b->last_jit_passes += jm->fn[p] != nullptr && !tabled[p];
+    });
+    if (rc == QSIM_OK && plain) return qsim_batch_run(b, gates, count, nullptr, 0, flags);
+    return rc;
+}
+
+int qsim_batch_sweep_plan(int n_qubits, int batch, const qsim_gate* gates, size_t count, int flags,
+                          int32_t info[8]) {
+    return guarded([&] {
+        if (!info) fail(QSIM_ERR_INVALID_ARGUMENT, "null info");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > QSIM_MAX_QUBITS_SINGLE)
+            fail(QSIM_ERR_INVALID_ARGUMENT, "Number of qubits must be between 1 and 30");
+        if (batch < 1) fail(QSIM_ERR_INVALID_ARGUMENT, "batch_size must be positive");
+        std::vector<size_t> slots;
+        const std::vector<qsim_gate> pg = sweep_arguments(n_qubits, gates, count, flags, slots);
+        for (int i = 0; i < 8; ++i) info[i] = 0;
+        info[0] = (int32_t)slots.size();
+        info[3] = (int32_t)count;
+        const uint64_t bytes = 64ull * (uint64_t)batch * (uint64_t)slots.size();
+        info[4] = (int32_t)(uint32_t)(bytes & 0xffffffffull);
+        info[5] = (int32_t)(uint32_t)(bytes >> 32);
+        const bool fused_path = sweep_fused_path(n_qubits, flags);
+        info[6] = fused_path ? 1 : 0;
+        if (!fused_path || count == 0) return;
+        const CtrlOutOff ctrl_off;
+        const Plan plan = plan_fused(sweep_lower(n_qubits, pg, {}, true), n_qubits);
+        info[1] = (int32_t)plan.passes.size();
+        for (size_t p = 0; p < plan.passes.size(); ++p) info[2] += pass_has_step_op(plan, p) ? 1 : 0;
+    });
+}
 
 int qsim_batch_create(int n_qubits, int batch_size, qsim_batch** out) {
     return guarded([&] {

@@ -433,11 +433,25 @@ struct FusedRange {
     double2* alt = nullptr;
 };
 // frames != null: batched noisy run under per-trajectory Pauli frames (FArgs::frames).
+// sweep != null (never together with frames): batched parameter sweep — an op with step >= 0 takes
+// its eight coefficients from sweep[(step * batch + member) * 8] (Op::m layout); a pass holding
+// such an op always runs the interpreter, never a circuit-specialised kernel.
 // Returns the buffer that holds the result (st, or range.alt after an odd number of relayout
 // passes).
 double2* launch_fused(double2* st, int n, uint64_t batch, const Plan& plan, const TileOp* d_ops,
                   const Stage* d_stages, hipStream_t s, Timer* tm, const JitModule* jm = nullptr,
-                  const uint64_t* frames = nullptr, const FusedRange& range = FusedRange());
+                  const uint64_t* frames = nullptr, const FusedRange& range = FusedRange(),
+                  const double* sweep = nullptr);
+// Does pass `pidx` of the plan hold an op with step >= 0 (a frame-conjugated or member-dependent op)?
+bool pass_has_step_op(const Plan& plan, size_t pidx);
+
+// Per-gate kernels of a batched parameter sweep (batch_sweep.hip): `op` (K_M1 or K_DIAG, any
+// control mask, any target, n >= 1) applied to every member of st ([batch][2^n]) with member t's
+// eight coefficients at coef[t * 8] (Op::m layout) instead of op.m.  One launch.  Asynchronous.
+void launch_sweep_op(double2* st, int n, uint64_t batch, const Op& op, const double* coef, hipStream_t s, Timer* tm);
+// The angle every parameterised gate of a sweep is planned under (the plan and the qubit layout
+// must not depend on the members' angles): no multiple of pi, so it lowers to S_GEN.
+constexpr double kSweepPlaceholderAngle = 0.7390851332151607;
 
 // Single-trajectory Monte-Carlo noise (noise.hip): one per-pair pass of channel `type`
 // (reference NoiseType numbering) on `qubit`, uniforms from the hash of (seed, counter, pair);

@@ -1068,7 +1068,13 @@ struct FArgs {
     double scale;        // applied at the store: (1/sqrt2)^(unnormalized H butterflies)
     // Pauli frames of a batched noisy run: frames[2 * (step * nbatch + traj)] = {F, G}, the
     // frame X^F Z^G (phase dropped) in force before circuit step `step` (batched.hip).
-    const uint64_t* frames;
+    // A parameter sweep's member table takes the same slot (the two never meet in one launch):
+    // table[(slot * nbatch + member) * 8 ..] = the eight coefficients (Op::m layout) member
+    // `member` applies its parameterised gate `slot` with (TileOp::step = slot).
+    union {
+        const uint64_t* frames;
+        const double* table;
+    };
     int nbatch;
     // Sub-space launch (sharded engine's overlapped remaps): tiles skip the fix_mask positions,
     // which read fix_val; zmask = fix_mask | the tile's own positions above the run.
@@ -1442,6 +1448,38 @@ __device__ __forceinline__ void stage_op_frame(double2 (&v)[1 << RB], uint32_t j
     }
 }
 
+// One op of a parameter sweep (batched.hip: qsim_batch_run_sweep): its 2x2 / diagonal comes from the
+// member table instead of op.m — table[(step * nbatch + member) * 8 ..], Op::m layout, the member
+// uniform over the tile, so the eight doubles are scalar loads (no per-lane traffic, no LDS).  The
+// general arms of the frame path with an empty frame: a rotation by 0 or pi is the general 2x2 too.
+template <int RB>
+__device__ __forceinline__ void stage_op_table(double2 (&v)[1 << RB], uint32_t jb, const TileOp& op,
+                                               const double* table, int nbatch, uint64_t member) {
+    const double* c = table + 8ull * ((uint64_t)op.step * (uint64_t)nbatch + member);
+    const double2 m0 = make_double2(ldc(c, 0), ldc(c, 1)), m1 = make_double2(ldc(c, 2), ldc(c, 3));
+    if (op.kind == K_DIAG) {  // d0 = m0, d1 = m1 on the control == 1 subspace
+        const uint32_t cr = op.cm_reg, ct = op.cm_thr;
+        const bool thr_ok = (jb & ct) == ct;
+        const bool tbit = ((jb >> op.b0) & 1u) != 0;
+#pragma unroll
+        for (int r = 0; r < (1 << RB); ++r) {
+            const bool bit = op.p0 >= 0 ? (((r >> op.p0) & 1) != 0) : tbit;
+            const bool ok = (((uint32_t)r & cr) == cr) && thr_ok;
+            const double2 d = make_double2(bit ? m1.x : m0.x, bit ? m1.y : m0.y);
+            v[r] = sel(ok, cmul(d, v[r]), v[r]);
+        }
+        return;
+    }
+    const double2 m2 = make_double2(ldc(c, 4), ldc(c, 5)), m3 = make_double2(ldc(c, 6), ldc(c, 7));
+    switch (op.p0) {
+        case 0: frame_m1_arm<RB, 0>(v, jb, op, m0, m1, m2, m3, 0u, 0u); break;
+        case 1: frame_m1_arm<RB, 1>(v, jb, op, m0, m1, m2, m3, 0u, 0u); break;
+        case 2: if constexpr (RB > 2) frame_m1_arm<RB, 2>(v, jb, op, m0, m1, m2, m3, 0u, 0u); break;
+        case 3: if constexpr (RB > 3) frame_m1_arm<RB, 3>(v, jb, op, m0, m1, m2, m3, 0u, 0u); break;
+        default: break;
+    }
+}
+
 // Thread index spread over the tile bits that are not the stage's register bits.
 template <int RB>
 __device__ __forceinline__ uint32_t stage_jb(const Stage& st) {
@@ -1456,7 +1494,8 @@ __device__ __forceinline__ uint32_t stage_jb(const Stage& st) {
 // register bits, so a wave still moves 64 consecutive amplitudes = one 1 KiB run per
 // instruction); only the stages in between round-trip through LDS (read, ops, write, barrier).
 // A pass whose ops fit one such stage never touches LDS.
-template <int H, bool NT, bool FR = false, int RBT = stage_rb(H)>
+// MT: a parameter sweep's pass — ops with step >= 0 read their matrix from the member table.
+template <int H, bool NT, bool FR = false, int RBT = stage_rb(H), bool MT = false>
 __global__ __launch_bounds__((64 << H) >> RBT, H >= 7 ? 1 : 2) void k_fused_staged(FArgs a) {  // LDS-bound: 2 WGs/CU (h <= 6), 1 at h = 7
     constexpr int T = 64 << H;
     constexpr int RB = RBT;
@@ -1513,6 +1552,13 @@ __global__ __launch_bounds__((64 << H) >> RBT, H >= 7 ? 1 : 2) void k_fused_stag
                 if (op.step < 0) stage_op<RB>(v, jb, op);  // Clifford: moved the frame instead
                 else stage_op_frame<RB>(v, jb, op, a.frames, a.nbatch, traj);
             }
+        } else if constexpr (MT) {  // (planned with every control in the tile: no cm_out here)
+            const uint64_t member = tile_id >> a.log_tpt;
+            for (int o = sg.op_begin; o < sg.op_end; ++o) {
+                const TileOp op = ldc(a.ops, o);
+                if (op.step < 0) stage_op<RB>(v, jb, op);
+                else stage_op_table<RB>(v, jb, op, a.table, a.nbatch, member);
+            }
         } else {
             for (int o = sg.op_begin; o < sg.op_end; ++o) {
                 const TileOp op = ldc(a.ops, o);
@@ -1566,9 +1612,25 @@ static uint64_t pipe_workgroups(int h) {
     return (uint64_t)cus * (uint64_t)(per > 0 ? per : (h >= 7 ? 1 : 2));
 }
 
+bool pass_has_step_op(const Plan& plan, size_t pidx) {
+    const FusedPass& p = plan.passes[pidx];
+    if (p.single >= 0) return plan.singles[p.single].src >= 0;
+    if (p.h < 4) {
+        for (int o = p.op_begin; o < p.op_end; ++o)
+            if (plan.ops[o].step >= 0) return true;
+        return false;
+    }
+    for (int k = p.stage_begin; k < p.stage_end; ++k)
+        for (int o = plan.stages[k].op_begin; o < plan.stages[k].op_end; ++o)
+            if (plan.ops[o].step >= 0) return true;
+    return false;
+}
+
 double2* launch_fused(double2* st, int n, uint64_t batch, const Plan& plan, const TileOp* d_ops,
                       const Stage* d_stages, hipStream_t s, Timer* tm, const JitModule* jm,
-                      const uint64_t* frames, const FusedRange& range) {
+                      const uint64_t* frames, const FusedRange& range, const double* sweep) {
+    if (sweep && (frames || range.fix_mask))
+        fail(QSIM_ERR_RUNTIME, "a parameter sweep runs whole passes without Pauli frames");
     double2* const home = st;
     const int nfix = __builtin_popcountll(range.fix_mask);
     const double pass_bytes = 32.0 * std::ldexp((double)(1ull << n), -nfix) * (double)batch;
@@ -1582,6 +1644,9 @@ double2* launch_fused(double2* st, int n, uint64_t batch, const Plan& plan, cons
             fail(QSIM_ERR_RUNTIME, "sub-space launch needs staged tile passes");
         if (frames && (p.single >= 0 || p.h < 4))
             fail(QSIM_ERR_RUNTIME, "Pauli-frame passes need staged tiles (n >= 10)");
+        const bool tabled = sweep && pass_has_step_op(plan, pidx);
+        if (tabled && (p.single >= 0 || p.h < 4 || p.relayout))
+            fail(QSIM_ERR_RUNTIME, "member-dependent ops need staged tile passes (n >= 10)");
         if (p.single >= 0) {
             launch_op(st, n, batch, plan.singles[p.single], s, tm);
             continue;
@@ -1650,6 +1715,28 @@ double2* launch_fused(double2* st, int n, uint64_t batch, const Plan& plan, cons
                 case 5: hipExtLaunchKernelGGL((k_fused_staged<5, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, ev0, ev1, 0, a); break;
                 case 6: hipExtLaunchKernelGGL((k_fused_staged<6, true, true>), dim3((unsigned)blocks), dim3(256), 0, s, ev0, ev1, 0, a); break;
                 default: hipExtLaunchKernelGGL((k_fused_staged<7, true, true>), dim3((unsigned)blocks), dim3(stage_threads(7)), 0, s, ev0, ev1, 0, a); break;
+            }
+            QSIM_HIPCHK(hipGetLastError());
+            continue;
+        }
+        if (tabled) {  // parameter sweep: the interpreter with the member table (a circuit-specialised
+                       // kernel would bake the placeholder matrix the pass was planned under)
+            for (int k = p.stage_begin; k < p.stage_end; ++k)
+                for (int o = plan.stages[k].op_begin; o < plan.stages[k].op_end; ++o)
+                    if (plan.ops[o].cm_out) fail(QSIM_ERR_RUNTIME, "sweep pass with a tile-constant control");
+            a.table = sweep;
+            a.nbatch = (int)batch;
+            if (p.rb != stage_rb(p.h)) {
+                if (p.h != 7 || p.rb != 3) fail(QSIM_ERR_RUNTIME, "sweep pass with an unsupported stage width");
+                hipExtLaunchKernelGGL((k_fused_staged<7, true, false, 3, true>), dim3((unsigned)blocks), dim3(1024), 0, s, ev0, ev1, 0, a);
+                QSIM_HIPCHK(hipGetLastError());
+                continue;
+            }
+            switch (p.h) {
+                case 4: hipExtLaunchKernelGGL((k_fused_staged<4, true, false, stage_rb(4), true>), dim3((unsigned)blocks), dim3(256), 0, s, ev0, ev1, 0, a); break;
+                case 5: hipExtLaunchKernelGGL((k_fused_staged<5, true, false, stage_rb(5), true>), dim3((unsigned)blocks), dim3(256), 0, s, ev0, ev1, 0, a); break;
+                case 6: hipExtLaunchKernelGGL((k_fused_staged<6, true, false, stage_rb(6), true>), dim3((unsigned)blocks), dim3(256), 0, s, ev0, ev1, 0, a); break;
+                default: hipExtLaunchKernelGGL((k_fused_staged<7, true, false, stage_rb(7), true>), dim3((unsigned)blocks), dim3(stage_threads(7)), 0, s, ev0, ev1, 0, a); break;
             }
             QSIM_HIPCHK(hipGetLastError());
             continue;

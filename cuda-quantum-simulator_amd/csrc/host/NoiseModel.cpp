@@ -164,6 +164,23 @@ void BatchedSimulator::run(const Circuit& circuit) {
                              (noise_ == BatchedNoise::Reference ? QSIM_BATCH_REFERENCE_NOISE : 0)));
 }
 
+void BatchedSimulator::runSweep(const Circuit& circuit, const std::vector<double>& angles) {
+    if (circuit.getNumQubits() != num_qubits_)
+        throw std::invalid_argument("Circuit qubit count doesn't match simulator");
+    if (!noise_model_.getChannels().empty())
+        throw std::invalid_argument("runSweep is noise-free: the noise model must be empty");
+    if (gate_set_ != BatchedGateSet::Full || noise_ != BatchedNoise::Physical)
+        throw std::invalid_argument("runSweep needs the full gate set and the physical noise semantics");
+    const std::vector<qsim_gate> gates = detail::toAbi(circuit);
+    size_t slots = 0;
+    for (const qsim_gate& g : gates)
+        slots += g.type == QSIM_GATE_RX || g.type == QSIM_GATE_RY || g.type == QSIM_GATE_RZ ||
+                 g.type == QSIM_GATE_CRY || g.type == QSIM_GATE_CRZ;
+    if (angles.size() != slots * (size_t)batch_size_)
+        throw std::invalid_argument("angles must hold batch_size x (parameterised gates) values");
+    check(qsim_batch_run_sweep(h_, gates.data(), gates.size(), angles.data(), slots, 0));
+}
+
 std::vector<double> BatchedSimulator::getAverageProbabilities() const {
     std::vector<double> p(size_t(1) << num_qubits_);
     check(qsim_batch_avg_probabilities(h_, p.data()));

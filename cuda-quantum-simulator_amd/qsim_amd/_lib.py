@@ -172,6 +172,8 @@ _sig(hip, "qsim_batch_set_seed", [_P, c_uint64])
 _sig(hip, "qsim_batch_set_trajectory_offset", [_P, c_uint64])
 _sig(hip, "qsim_batch_run", [_P, POINTER(qsim_gate), c_size_t, POINTER(qsim_noise_channel),
                              c_size_t, c_int])
+_sig(hip, "qsim_batch_run_sweep", [_P, POINTER(qsim_gate), c_size_t, POINTER(c_double), c_size_t, c_int])
+_sig(hip, "qsim_batch_sweep_plan", [c_int, c_int, POINTER(qsim_gate), c_size_t, c_int, POINTER(c_int32)])
 _sig(hip, "qsim_batch_avg_probabilities", [_P, _P])
 _sig(hip, "qsim_batch_traj_probabilities", [_P, c_int, _P])
 _sig(hip, "qsim_batch_traj_state", [_P, c_int, _P])

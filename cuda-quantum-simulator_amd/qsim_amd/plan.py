@@ -273,6 +273,26 @@ def gradient_plan(circuit: Circuit, observable):
     return p.value, s.value, a.value
 
 
+def parameterised_slots(circuit: Circuit):
+    """Gate indices of the circuit's parameterised gates (Rx, Ry, Rz, CRY, CRZ) in gate order: slot
+    k of BatchedSimulator.runSweep, i.e. column k of its angles, is gate parameterised_slots()[k]."""
+    from .circuit import PARAMETRIC
+    return [i for i, op in enumerate(circuit.getGates()) if op.type in PARAMETRIC]
+
+
+def batch_sweep_plan(circuit: Circuit, batch_size: int, per_gate: bool = False) -> dict:
+    """What BatchedSimulator.runSweep would do for this circuit on batch_size members, planned
+    under the identity layout (qsim_batch_sweep_plan, host only): slots, passes, member_passes (the
+    passes holding a member-dependent op; they run the pass interpreter), per_gate_launches,
+    table_bytes (64 per slot and member) and fused (False: one launch per gate)."""
+    arr, cnt = circuit.to_abi()
+    info = (ctypes.c_int32 * 8)()
+    flags = _lib.QSIM_BATCH_PER_GATE if per_gate else 0
+    _lib.check(_lib.hip.qsim_batch_sweep_plan(circuit.getNumQubits(), int(batch_size), arr, cnt, flags, info))
+    return {"slots": info[0], "passes": info[1], "member_passes": info[2], "per_gate_launches": info[3],
+            "table_bytes": (info[4] & 0xffffffff) | ((info[5] & 0xffffffff) << 32), "fused": bool(info[6])}
+
+
 def _perm_arg(n: int, perm):
     if perm is None:
         return None

@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib
-from .circuit import Circuit, GateOp, is_valid_qubit_count, MAX_QUBITS, MIN_QUBITS
+from .circuit import Circuit, GateOp, is_valid_qubit_count, MAX_QUBITS, MIN_QUBITS, PARAMETRIC
 from .observable import PauliSum, trotter_sequence
 
 _c = ctypes
@@ -708,6 +708,32 @@ class BatchedSimulator:
         flags = int(self._gate_set) | int(self._noise_sem) | \
             (_lib.QSIM_BATCH_PER_GATE if per_gate else 0)
         _lib.check(_lib.hip.qsim_batch_run(self._h, g, ng, ch, nch, flags))
+
+    def runSweep(self, circuit: Circuit, angles, per_gate: bool = False) -> None:
+        """One circuit, one angle set per member (qsim_batch_run_sweep; no reference counterpart).
+        angles: array-like of shape (B, P), or (P,) given to every member; P = the circuit's
+        parameterised gates (Rx, Ry, Rz, CRY, CRZ) in gate order (plan.parameterised_slots): member
+        t applies its k-th one with angles[t, k], the angles stored in the circuit are ignored.
+        Noise-free, from whatever every member holds; one planned run whatever the angles.
+        ValueError: a shape mismatch, a non-empty noise model, the reference gate set or the
+        reference noise semantics selected (construct with noise=BatchedNoise.Physical)."""
+        if circuit.getNumQubits() != self._n:
+            raise ValueError("Circuit qubit count doesn't match simulator")
+        if self._noise.to_abi()[1] > 0:
+            raise ValueError("runSweep is noise-free: the noise model must be empty")
+        if self._gate_set != BatchedGateSet.Full or self._noise_sem != BatchedNoise.Physical:
+            raise ValueError("runSweep needs the full gate set and the physical noise semantics")
+        g, ng = circuit.to_abi()
+        n_slots = sum(1 for op in circuit.getGates() if op.type in PARAMETRIC)
+        a = np.asarray(angles, dtype=np.float64)
+        if a.ndim == 1:
+            a = np.broadcast_to(a, (self._b, a.shape[0]))
+        if a.ndim != 2 or a.shape != (self._b, n_slots):
+            raise ValueError(f"angles must have shape ({self._b}, {n_slots}) or ({n_slots},)")
+        a = np.ascontiguousarray(a)
+        flags = _lib.QSIM_BATCH_PER_GATE if per_gate else 0
+        _lib.check(_lib.hip.qsim_batch_run_sweep(self._h, g, ng, a.ctypes.data_as(_c.POINTER(_c.c_double)),
+                                                 n_slots, flags))
 
     def synchronize(self) -> None: _lib.check(_lib.hip.qsim_batch_sync(self._h))
 

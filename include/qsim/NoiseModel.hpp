@@ -134,6 +134,14 @@ public:
     void setTrajectoryOffset(unsigned long long first);
     void reset();
     void run(const Circuit& circuit);
+    // Parameter sweep (no reference counterpart; qsim_batch_run_sweep): one circuit, one angle set
+    // per trajectory.  angles is trajectory-major, B x P, P = the circuit's parameterised gates
+    // (Rx, Ry, Rz, CRY, CRZ) in gate order: trajectory t applies its k-th one with
+    // angles[t * P + k]; the angles stored in the circuit are ignored.  Noise-free, from whatever
+    // every trajectory holds.  std::invalid_argument on a size mismatch, or when a noise model,
+    // the reference gate set or the reference noise semantics is configured (a sweep needs
+    // setNoiseSemantics(BatchedNoise::Physical) and an empty noise model).
+    void runSweep(const Circuit& circuit, const std::vector<double>& angles);
 
     std::vector<double> getAverageProbabilities() const;
     std::vector<double> getProbabilities(int trajectory_idx) const;  // std::out_of_range

@@ -505,6 +505,42 @@ enum { QSIM_BATCH_FULL_GATESET = 0, QSIM_BATCH_REFERENCE_GATESET = 1, QSIM_BATCH
  * hash of qsim_noise_apply keyed by (seed, pass counter, global pair index t*2^(n-1) + pair). */
 int qsim_batch_run(qsim_batch* b, const qsim_gate* gates, size_t count,
                    const qsim_noise_channel* channels, size_t n_channels, int flags);
+/* Parameter sweep (no reference counterpart): one circuit, one angle set per member.  P = number
+ * of parameterised gates (Rx, Ry, Rz, CRY, CRZ) of the list, in list order ("slots").  angles is
+ * member-major, B x P: member t applies its k-th parameterised gate with angles[t * P + k]; the
+ * `parameter` field of those gates is ignored.  Every other gate is applied to all members as
+ * qsim_batch_run applies it.
+ * Noise-free: no channel list; carried Pauli frames of an earlier noisy run are applied to the
+ * stored vectors first, as a reader of the state does; trajectory offset, seed and step counter are
+ * neither read nor advanced.  Starts from whatever each member holds (|0..0> after reset, or the
+ * result of an earlier run or sweep).  Asynchronous, like qsim_batch_run.  Bitwise reproducible.
+ * flags: 0 or QSIM_BATCH_PER_GATE; QSIM_BATCH_REFERENCE_GATESET / QSIM_BATCH_REFERENCE_NOISE ->
+ * QSIM_ERR_INVALID_ARGUMENT (the reference gate set has no rotations to sweep).  n_slots != P, or
+ * null angles with P > 0, or an angle that is not finite -> QSIM_ERR_INVALID_ARGUMENT.  Gates are
+ * validated as qsim_batch_run validates them, before the first launch.  P == 0 behaves exactly as
+ * qsim_batch_run(b, gates, count, NULL, 0, flags) (angles may be null); count == 0 launches
+ * nothing.
+ * For n >= 10 (without QSIM_BATCH_PER_GATE, QSIM_BATCH_FUSED=0) the circuit runs as the fused tile
+ * passes of qsim_batch_run; a pass that holds a parameterised gate always runs the pass
+ * interpreter, which reads that gate's 2x2 per member from a coefficient table, the others run
+ * what they run in qsim_batch_run (circuit-specialised kernels included).  Otherwise one launch
+ * per gate over all members.  The plan and the qubit layout are made for the list with every
+ * parameterised angle replaced by one fixed placeholder: a second sweep of the same circuit with
+ * new angles plans nothing.
+ * The coefficient table (64 bytes per slot and member: the gate's eight matrix doubles, lowered on
+ * the host exactly as qsim_run lowers the rotation) lives on the batch object, grows on demand and
+ * is freed with it; it is counted by no memory figure.  If it cannot be allocated:
+ * QSIM_ERR_DEVICE, the states untouched. */
+int qsim_batch_run_sweep(qsim_batch* b, const qsim_gate* gates, size_t count,
+                         const double* angles, size_t n_slots, int flags);
+/* Host-only (no GPU): what the call above would do for a batch of `batch` members, planned under
+ * the identity layout and the tile height in force.  info[0] = P; [1] = tile passes; [2] = passes
+ * holding at least one member-dependent op (always the interpreter); [3] = launches of the
+ * per-gate path (one per gate); [4], [5] = table bytes (64 * batch * P), low and high word;
+ * [6] = 1 if the fused path is taken (n >= 10, no QSIM_BATCH_PER_GATE), else 0 and [1] = [2] = 0;
+ * [7] = 0.  The argument errors of the run. */
+int qsim_batch_sweep_plan(int n_qubits, int batch, const qsim_gate* gates, size_t count, int flags,
+                          int32_t info[8]);
 int qsim_batch_avg_probabilities(qsim_batch* b, double* dst);           /* 2^n */
 int qsim_batch_traj_probabilities(qsim_batch* b, int traj, double* dst);  /* 2^n */
 int qsim_batch_traj_state(qsim_batch* b, int traj, double* dst);          /* 2*2^n */

@@ -13,6 +13,12 @@
 // pure-state trajectory; statistics, not per-trajectory realizations, match the reference.
 // Channel types the reference batched mode ignores (F5: only Depolarizing) are Pauli-free here
 // too: BitFlip/PhaseFlip/BitPhaseFlip are applied (X/Z/Y), damping channels are ignored.
+//
+// qsim_batch_run validates, decides the path and lowers; the paths are run_reference_noise (the
+// reference's per-pair process: run_pulled, run_tile with split_tile_run, or step by step — the
+// schedules and their side kit, NoiseSide, are noise.hip's), run_frames (fused passes under Pauli
+// frames) and run_per_gate.  Every fused run — those, a sweep's, canonicalize's SWAP network —
+// goes through run_planned.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -268,51 +274,42 @@ struct qsim_batch {
     // its frame build from them (frames compose: no Pauli pass per run); everything that reads
     // or writes amplitudes otherwise materialises them first (materialize), and so does sync.
     bool frame_pending = false;
-    // Pulled reference noise (noise.hip: launch_pull_noise_step) writes out of place: the
+    // Pulled reference noise (noise.hip: launch_pull_noise_run) writes out of place: the
     // ensemble alternates between d0 (allocated at create) and d1 (allocated on the first pulled
     // run when the device has room; otherwise the push kernels run).  d is the current one.
     // pinned: a raw pointer to d0 was handed out, so a run that ends in d1 copies back.
     double2* d0 = nullptr;
     double2* d1 = nullptr;
-    // Two sets of per-step code words (one per amplitude; noise steps alternate), so the next
-    // step's words are built on map_stream while this step's pass runs.
-    unsigned char* d_codes = nullptr;
-    size_t codes_cap = 0;           // bytes of ONE set
-    // Two sets of per-step flip lists of the in-tile noise kernel (noise.hip: k_gn_lists), built
-    // on map_stream one step ahead.
-    char* d_lists = nullptr;
-    size_t lists_cap = 0;           // bytes of ONE set
-    // QSIM_NOISE_SPLIT=k (default 2): the in-tile path runs the ensemble as k trajectory parts on
-    // k streams (part 0 on `stream`), so one part's tile pass can overlap another's suffix push
-    struct SplitPart {
-        hipStream_t s = nullptr, ms = nullptr;
-        hipEvent_t built[2] = {}, used[2] = {}, start = nullptr, fork = nullptr, join = nullptr;
-        char* lists = nullptr;
-        size_t cap = 0;
-    };
-    std::vector<SplitPart> split;
-    hipStream_t map_stream = nullptr;
-    hipEvent_t ev_map[2] = {}, ev_pull[2] = {}, ev_start = nullptr;
     bool pinned = false;
+    // The side stream, events, code words and flip lists of the pulled and in-tile runs (both
+    // build one or two steps ahead of the passes that read them).
+    NoiseSide noise;
+    // QSIM_NOISE_SPLIT=k (default 2, at most 4): the in-tile path runs the ensemble as k trajectory
+    // parts on k streams (part 0 on `stream` with `noise`), so one part's tile pass can overlap
+    // another's suffix push; split[j - 1] is part j
+    struct SplitPart {
+        hipStream_t s = nullptr;
+        hipEvent_t fork = nullptr, join = nullptr;
+        NoiseSide side;
+        void destroy() noexcept {
+            if (s) (void)hipStreamSynchronize(s);
+            side.destroy();
+            for (hipEvent_t* e : {&fork, &join}) {
+                if (*e) (void)hipEventDestroy(*e);
+                *e = nullptr;
+            }
+            if (s) (void)hipStreamDestroy(s);
+            s = nullptr;
+        }
+        ~SplitPart() { destroy(); }
+    };
+    SplitPart split[3];
     ~qsim_batch() {
         if (stream) (void)hipStreamSynchronize(stream);
-        if (map_stream) (void)hipStreamSynchronize(map_stream);
-        for (hipEvent_t e : {ev_map[0], ev_map[1], ev_pull[0], ev_pull[1], ev_start})
-            if (e) (void)hipEventDestroy(e);
-        if (map_stream) (void)hipStreamDestroy(map_stream);
+        noise.destroy();
         if (d0) (void)hipFree(d0);
         if (d1) (void)hipFree(d1);
-        if (d_codes) (void)hipFree(d_codes);
-        if (d_lists) (void)hipFree(d_lists);
-        for (SplitPart& p : split) {
-            if (p.s) (void)hipStreamSynchronize(p.s);
-            if (p.ms) (void)hipStreamSynchronize(p.ms);
-            for (hipEvent_t e : {p.built[0], p.built[1], p.used[0], p.used[1], p.start, p.fork, p.join})
-                if (e) (void)hipEventDestroy(e);
-            if (p.s) (void)hipStreamDestroy(p.s);
-            if (p.ms) (void)hipStreamDestroy(p.ms);
-            if (p.lists) (void)hipFree(p.lists);
-        }
+        for (SplitPart& p : split) p.destroy();
         if (d_xz) (void)hipFree(d_xz);
         if (d_e) (void)hipFree(d_e);
         if (d_ch) (void)hipFree(d_ch);
@@ -333,110 +330,45 @@ void settle_in_d0(qsim_batch* b) {
                                hipMemcpyDeviceToDevice, b->stream));
     b->d = b->d0;
 }
-// map_stream and its events (the pulled path's word maps, the tile path's flip lists).
-void ensure_map_stream(qsim_batch* b) {
-    if (b->map_stream) return;
-    // QSIM_NOISE_STREAM_PRIO (experiments): 1 = the side stream at the lowest priority, so the
-    // list builds yield the CUs to the main stream's kernels
-    const char* pe = std::getenv("QSIM_NOISE_STREAM_PRIO");
-    if (pe && std::atoi(pe) != 0) {
-        int lo = 0, hi = 0;
-        QSIM_HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
-        QSIM_HIPCHK(hipStreamCreateWithPriority(&b->map_stream, hipStreamNonBlocking, lo));
-    } else {
-        QSIM_HIPCHK(hipStreamCreateWithFlags(&b->map_stream, hipStreamNonBlocking));
-    }
-    for (hipEvent_t* e : {&b->ev_map[0], &b->ev_map[1], &b->ev_pull[0], &b->ev_pull[1], &b->ev_start})
-        QSIM_HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+// The qubit count whose state has as many amplitudes as the whole ensemble (rounded up): what the
+// relabeling and JIT size thresholds are applied to.
+int batch_eff_qubits(const qsim_batch* b) {
+    int eff = b->n;
+    while ((1ll << (eff - b->n)) < (long long)b->batch) ++eff;
+    return eff;
 }
-// Two sets of flip lists of `bytes` each, when the device has room beside a margin (false: the
-// tile kernels walk the blocks themselves).
-bool ensure_list_buffers(qsim_batch* b, size_t bytes) {
-    if (bytes > b->lists_cap) {
-        if (b->d_lists) {
-            QSIM_HIPCHK(hipStreamSynchronize(b->stream));
-            if (b->map_stream) QSIM_HIPCHK(hipStreamSynchronize(b->map_stream));
-            (void)hipFree(b->d_lists);
-            b->d_lists = nullptr;
-            b->lists_cap = 0;
-        }
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (free_b < 2 * bytes + (256ull << 20)) return false;
-        if (hipMalloc((void**)&b->d_lists, 2 * bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            b->d_lists = nullptr;
-            return false;
-        }
-        b->lists_cap = bytes;
-    }
-    ensure_map_stream(b);
-    return true;
-}
+// QSIM_NOISE_STREAM_PRIO (experiments): 1 = the side stream at the lowest priority, so the
+// list builds yield the CUs to the main stream's kernels
+void ensure_side_stream(qsim_batch* b) { b->noise.ensure_stream(env_switch("QSIM_NOISE_STREAM_PRIO", false)); }
 // The in-tile run over k trajectory parts on k streams (QSIM_NOISE_SPLIT, default 2): part 0 on the object's
-// stream with its list sets, part j > 0 on a stream of its own with its own side stream and lists;
-// every part draws with the global pair index, so the states are the one-part run's.  false (nothing
-// launched): a part's list buffers do not fit beside the margin ensure_list_buffers keeps — the
-// caller runs the ensemble as one part instead (a near-full device must not turn a run
-// that fits as one part into an error).
-bool split_tile_run(qsim_batch* b, const std::vector<Op>& ops, const std::vector<NoiseChan>& dep, int k,
-                    const GnLists& L0) {
+// stream with its list sets (the caller has ensured them), part j > 0 on a stream of its own with its
+// own side kit; every part draws with the global pair index, so the states are the one-part run's.
+// false (nothing launched): a part's lists do not fit beside the margin NoiseSide::ensure_lists
+// keeps — the caller runs the ensemble as one part instead (a near-full device must not
+// turn a run that fits as one part into an error).
+bool split_tile_run(qsim_batch* b, const std::vector<Op>& ops, const std::vector<NoiseChan>& dep, int k) {
     const uint64_t B = (uint64_t)b->batch;
-    if ((int)b->split.size() < k - 1) b->split.resize(k - 1);
-    const uint64_t c0 = b->ncounter;
-    uint64_t c_end = c0;
-    std::vector<GnLists> Ls(k);
     std::vector<uint64_t> first(k + 1);
     for (int j = 0; j <= k; ++j) first[j] = B * (uint64_t)j / (uint64_t)k;
-    Ls[0] = L0;
     for (int j = 1; j < k; ++j) {  // every part's list buffers first, so a refusal launches nothing
         qsim_batch::SplitPart& p = b->split[j - 1];
-        const size_t lb = gate_noise_lists_bytes(b->n, first[j + 1] - first[j], dep);
-        if (lb <= p.cap) continue;
-        if (p.lists) {
-            QSIM_HIPCHK(hipStreamSynchronize(p.s));
-            QSIM_HIPCHK(hipStreamSynchronize(p.ms));
-            (void)hipFree(p.lists);
-            p.lists = nullptr;
-            p.cap = 0;
-        }
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (free_b < 2 * lb + (256ull << 20)) return false;
-        if (hipMalloc((void**)&p.lists, 2 * lb) != hipSuccess) {
-            (void)hipGetLastError();
-            p.lists = nullptr;
-            return false;
-        }
-        p.cap = lb;
+        if (!p.side.ensure_lists(gate_noise_lists_bytes(b->n, first[j + 1] - first[j], dep), p.s)) return false;
     }
+    std::vector<GnLists> Ls(k);
+    Ls[0] = b->noise.view();
     for (int j = 1; j < k; ++j) {
         qsim_batch::SplitPart& p = b->split[j - 1];
         if (!p.s) {
             QSIM_HIPCHK(hipStreamCreateWithFlags(&p.s, hipStreamNonBlocking));
-            QSIM_HIPCHK(hipStreamCreateWithFlags(&p.ms, hipStreamNonBlocking));
-            for (hipEvent_t* e : {&p.built[0], &p.built[1], &p.used[0], &p.used[1], &p.start, &p.fork, &p.join})
-                QSIM_HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+            for (hipEvent_t* e : {&p.fork, &p.join}) QSIM_HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         }
-        GnLists& L = Ls[j];
-        L.buf[0] = p.lists;
-        L.buf[1] = p.lists + p.cap;
-        L.set_bytes = p.cap;
-        L.ms = p.ms;
-        L.built[0] = p.built[0];
-        L.built[1] = p.built[1];
-        L.used[0] = p.used[0];
-        L.used[1] = p.used[1];
-        L.start = p.start;
+        p.side.ensure_stream(false);
+        Ls[j] = p.side.view();
         QSIM_HIPCHK(hipEventRecord(p.fork, b->stream));  // (after everything before this run)
         QSIM_HIPCHK(hipStreamWaitEvent(p.s, p.fork, 0));
     }
+    const uint64_t c0 = b->ncounter;
+    uint64_t c_end = c0;
     for (int j = 0; j < k; ++j) {
         hipStream_t sj = j == 0 ? b->stream : b->split[j - 1].s;
         uint64_t c = c0;
@@ -451,46 +383,21 @@ bool split_tile_run(qsim_batch* b, const std::vector<Op>& ops, const std::vector
     b->ncounter = c_end;
     return true;
 }
-// Buffers of the pulled noise path (second ensemble buffer, flip codes, touched bits), allocated
+// Buffers of the pulled noise path (second ensemble buffer, two sets of code words), allocated
 // when the device has room for them beside a margin; false: run the push kernels instead.
 bool ensure_pull_buffers(qsim_batch* b, size_t nch) {
-    const uint64_t amps = (uint64_t)b->batch << b->n;
-    const size_t state_b = amps * sizeof(double2);
+    const size_t state_b = ((uint64_t)b->batch * sizeof(double2)) << b->n;
     const size_t codes_b = pull_noise_codes_bytes(b->n, (uint64_t)b->batch, nch);
-    size_t need_b = (b->d1 ? 0 : state_b) + (codes_b > b->codes_cap ? 2 * codes_b : 0);
+    const size_t need_b = (b->d1 ? 0 : state_b) + (codes_b > b->noise.codes_cap ? 2 * codes_b : 0);
     if (need_b == 0) return true;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    if (free_b < need_b + (256ull << 20)) return false;
-    auto grab = [&](void** p, size_t bytes) {
-        if (hipMalloc(p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            *p = nullptr;
-            return false;
-        }
-        return true;
-    };
-    if (!b->d1 && !grab((void**)&b->d1, state_b)) return false;
-    if (codes_b > b->codes_cap) {
-        if (b->d_codes) {
-            QSIM_HIPCHK(hipStreamSynchronize(b->stream));
-            (void)hipFree(b->d_codes);
-            b->d_codes = nullptr;
-            b->codes_cap = 0;
-        }
-        if (!grab((void**)&b->d_codes, 2 * codes_b)) return false;
-        b->codes_cap = codes_b;
-    }
-    ensure_map_stream(b);
+    if (device_free_bytes() < need_b + kAltMarginBytes) return false;
+    if (!b->d1 && !(b->d1 = (double2*)device_alloc_or_null(state_b))) return false;
+    if (!b->noise.ensure_codes(codes_b, b->stream)) return false;
+    ensure_side_stream(b);
     return true;
 }
-// Apply the carried Pauli frames to the stored vectors (one pass), frames back to 1.
-void materialize(qsim_batch* b) {
-    if (!b->frame_pending) return;
-    b->frame_pending = false;
+// One Pauli pass: every trajectory's string (d_xz, d_e) applied to its stored vector.
+void apply_frames(qsim_batch* b) {
     const uint64_t N = 1ull << b->n;
     const uint64_t items_per_traj = N / 2 > 0 ? N / 2 : 1;
     const uint64_t total = items_per_traj * (uint64_t)b->batch;
@@ -498,6 +405,51 @@ void materialize(qsim_batch* b) {
     hipLaunchKernelGGL(k_pauli_apply, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, b->stream, b->d, b->n,
                        b->d_xz, b->d_e, items_per_traj, (uint64_t)b->batch);
     QSIM_HIPCHK(hipGetLastError());
+}
+// Apply the carried Pauli frames to the stored vectors (one pass), frames back to 1.
+void materialize(qsim_batch* b) {
+    if (!b->frame_pending) return;
+    b->frame_pending = false;
+    apply_frames(b);
+}
+// `ops` over every member as fused tile passes, through the plan cache.  frames: the Pauli frames
+// its ops with a step are conjugated by (null: none); table: a sweep's coefficient table (null:
+// none) — the passes that read it run in the interpreter, so circuit-specialised kernels are
+// looked up only when another pass exists and only those are counted.  counted = false (the SWAP
+// network of canonicalize): no circuit-specialised kernels, and the last run's figures stay.
+void run_planned(qsim_batch* b, const std::vector<Op>& ops, const uint64_t* frames, const double* table,
+                 bool counted = true) {
+    PlanCache::Entry& pe = b->plans.get(ops, b->n, b->stream);
+    const Plan& plan = pe.plan;
+    std::vector<char> tabled(plan.passes.size(), 0);
+    bool any_plain = table == nullptr;
+    for (size_t p = 0; table && p < plan.passes.size(); ++p) {
+        tabled[p] = pass_has_step_op(plan, p);
+        any_plain = any_plain || !tabled[p];
+    }
+    // (the JIT threshold counts the whole batch)
+    const JitModule* jm = counted && any_plain ? jit_for(pe.jit, plan, batch_eff_qubits(b)) : nullptr;
+    b->ops.upload(plan.ops.data(), plan.ops.size() * sizeof(TileOp), b->stream);
+    b->stages.upload(plan.stages.data(), plan.stages.size() * sizeof(Stage), b->stream);
+    launch_fused(b->d, b->n, (uint64_t)b->batch, plan, (const TileOp*)b->ops.ptr, (const Stage*)b->stages.ptr,
+                 b->stream, &b->timer, jm, frames, FusedRange(), table);
+    if (!counted) return;
+    b->last_passes = (int)plan.passes.size();
+    b->last_jit_passes = 0;
+    if (jm)
+        for (size_t p = 0; p < jm->fn.size(); ++p)
+            b->last_jit_passes += jm->fn[p] != nullptr && !(p < tabled.size() && tabled[p]);
+}
+// The layout of the first fused run of |0..0> members: the one the model prefers for the circuit
+// (lower_under: its ops under a candidate labeling), memoised per (kind, key).  The tile-control
+// rule in force (CtrlOutOff) is the caller's: the choice is made and memoised under it.
+void choose_first_layout(qsim_batch* b, int kind, const void* key, size_t key_bytes,
+                         const std::function<std::vector<Op>(const std::vector<int>&)>& lower_under) {
+    // relabel for the plan's tile layouts when the whole batch is HBM-sized
+    if (!relabel_enabled(batch_eff_qubits(b))) return;
+    if (layout_memo_get(b->n, kind, key, key_bytes, b->perm)) return;
+    b->perm = choose_layout(b->n, lower_under, relabel_tries()).perm;
+    layout_memo_put(b->n, kind, key, key_bytes, b->perm);
 }
 // Undo the relabeling in every trajectory (fused SWAP network over the batch, exact data
 // movement) before anything reads or writes amplitudes by index; carried frames first.
@@ -525,11 +477,7 @@ void canonicalize(qsim_batch* b) {
     }
     b->perm.clear();
     if (swaps.empty()) return;
-    PlanCache::Entry& pe = b->plans.get(swaps, n, b->stream);
-    b->ops.upload(pe.plan.ops.data(), pe.plan.ops.size() * sizeof(TileOp), b->stream);
-    b->stages.upload(pe.plan.stages.data(), pe.plan.stages.size() * sizeof(Stage), b->stream);
-    launch_fused(b->d, n, (uint64_t)b->batch, pe.plan, (const TileOp*)b->ops.ptr, (const Stage*)b->stages.ptr,
-                 b->stream, &b->timer);
+    run_planned(b, swaps, nullptr, nullptr, false);
 }
 // ---- parameter sweeps (qsim_batch_run_sweep / qsim_batch_sweep_plan) ----
 // The checks both entries share.  Returns the gate list with every parameterised gate's angle
@@ -560,6 +508,139 @@ std::vector<Op> sweep_lower(int n, const std::vector<qsim_gate>& pg, const std::
     int k = 0;
     for (size_t i = 0; i < ops.size(); ++i) ops[i].src = slots && gate_is_parameterised(pg[i].type) ? k++ : -1;
     return ops;
+}
+// ---- the paths of qsim_batch_run ----
+// Reference noise, pulled: the noise after gate i is applied by gate i+1's pass (out of place), the
+// noise after the last gate by one identity pass; same draws, same states as the push kernels.
+// false: not this run (unsupported channels, or no room for the buffers): nothing launched.
+bool run_pulled(qsim_batch* b, const std::vector<Op>& ops, const std::vector<NoiseChan>& dep) {
+    if (!pull_noise_supported(b->n, dep, false) || !ensure_pull_buffers(b, dep.size())) return false;
+    // QSIM_NOISE_MAP_OVERLAP=0: the word maps on the object's stream, one set in turn (read per run)
+    const bool overlap = env_switch("QSIM_NOISE_MAP_OVERLAP", true);
+    const uint64_t c0 = b->ncounter;
+    b->ncounter += (uint64_t)ops.size() * dep.size();  // (one pass counter per channel entry, as the push path)
+    double2* const buf[2] = {b->d0, b->d1};
+    b->d = buf[launch_pull_noise_run(buf, b->d == b->d0 ? 0 : 1, b->n, (uint64_t)b->batch, b->traj0, ops, dep, b->seed,
+                                     c0, b->noise, b->stream, &b->timer, overlap)];
+    if (b->pinned) settle_in_d0(b);
+    return true;
+}
+// Reference noise, in-tile (noise.hip: gate + in-tile channels in LDS per step, each step's flip
+// lists built on the side stream during the step before, when the device has room for them).
+// false: a gate the tile kernel does not take: nothing launched.
+bool run_tile(qsim_batch* b, const std::vector<Op>& ops, const std::vector<NoiseChan>& dep) {
+    bool all_tile = !ops.empty();
+    for (const Op& op : ops) all_tile = all_tile && gate_noise_tile_supported(b->n, op.kind >= 0 ? &op : nullptr);
+    if (!all_tile) return false;
+    const size_t lb = gate_noise_lists_bytes(b->n, (uint64_t)b->batch, dep);
+    GnLists L{};
+    const bool lists = lb && b->noise.ensure_lists(lb, b->stream);
+    if (lists) {
+        ensure_side_stream(b);
+        L = b->noise.view();
+    }
+    // two trajectory halves on two streams (QSIM_NOISE_SPLIT, read per run; default 2):
+    // one half's tile pass overlaps the other's DRAM-random suffix push — W-BATCH config 4
+    // 57.8 -> 54.1 ms per step (3 parts 62.5, 4 parts 58.6)
+    const int k = std::max(1, std::min(4, env_int("QSIM_NOISE_SPLIT", 2)));
+    if (k > 1 && b->batch >= k && lists && split_tile_run(b, ops, dep, k)) return true;
+    launch_gate_noise_run(b->d, b->n, (uint64_t)b->batch, b->traj0, ops, dep, b->seed, b->ncounter, b->stream,
+                          &b->timer, lists ? &L : nullptr);
+    return true;
+}
+// The reference's process (src/NoiseModel.cu:815-892): each gate, then for every Depolarizing
+// channel entry (the only type batched mode applies, F5) one pass over all B x 2^(n-1) amplitude
+// pairs; every pair draws its own uniform (counter hash of (seed, pass, global pair index) in
+// place of its curandState) and, below p, a second one picks X / Y / Z at 1/3, 2/3 — applied to
+// that pair only (F7).  Three schedules of the same draws: pulled, in-tile, or step by step.
+void run_reference_noise(qsim_batch* b, const std::vector<Op>& ops, const std::vector<NoiseChan>& dep) {
+    if (run_pulled(b, ops, dep) || run_tile(b, ops, dep)) return;
+    for (const Op& op : ops) {
+        const Op* o = op.kind >= 0 ? &op : nullptr;
+        if (gate_noise_tile_supported(b->n, o)) {  // (noise.hip: gate + in-tile channels in LDS)
+            launch_gate_noise_step(b->d, b->n, (uint64_t)b->batch, b->traj0, o, dep, b->seed, b->ncounter, b->stream,
+                                   &b->timer);
+            continue;
+        }
+        if (o) launch_op(b->d, b->n, (uint64_t)b->batch, op, b->stream, &b->timer);
+        launch_noise_after_gate(b->d, b->n, dep, b->seed, b->ncounter, b->stream, &b->timer, (uint64_t)b->batch,
+                                b->traj0);
+    }
+}
+// The Pauli frames of a run of `count` steps with `nch` channels (in d_ch): every draw, then per
+// trajectory the frame in force before each step (cl: the steps whose Clifford gate moves it).
+void build_frames(qsim_batch* b, size_t count, size_t nch, const std::vector<StepClifford>& cl) {
+    const size_t need_frames = 2 * count * (size_t)b->batch;
+    if (need_frames > b->frames_cap) {
+        QSIM_HIPCHK(hipStreamSynchronize(b->stream));
+        if (b->d_frames) QSIM_HIPCHK(hipFree(b->d_frames));
+        if (b->d_fe) QSIM_HIPCHK(hipFree(b->d_fe));
+        b->d_frames = nullptr;
+        b->d_fe = nullptr;
+        QSIM_HIPCHK(hipMalloc((void**)&b->d_frames, need_frames * sizeof(uint64_t)));
+        QSIM_HIPCHK(hipMalloc((void**)&b->d_fe, need_frames / 2 * sizeof(int)));
+        b->frames_cap = need_frames;
+    }
+    TimedLaunch tl(&b->timer, "pauli_frames", 0.0, b->stream);
+    const uint64_t draws = (uint64_t)count * b->batch;
+    hipLaunchKernelGGL(k_draw_steps, dim3((unsigned)((draws + 255) / 256)), dim3(256), 0, b->stream, b->d_ch, (int)nch,
+                       b->seed, b->step, (int)count, b->batch, b->traj0, b->d_frames, b->d_fe);
+    b->cliff.upload(cl.data(), cl.size() * sizeof(StepClifford), b->stream);
+    hipLaunchKernelGGL(k_frame_build, dim3((b->batch + 63) / 64), dim3(64), 0, b->stream, (int)count, b->batch,
+                       b->d_frames, b->d_fe, (const StepClifford*)b->cliff.ptr, b->d_xz, b->d_e,
+                       b->frame_pending ? 1 : 0);
+    QSIM_HIPCHK(hipGetLastError());
+}
+// Fused tile passes over all trajectories (a tile never straddles two).  Noise is carried as
+// per-trajectory Pauli frames: no noise kernel per gate, one frame build before the circuit and
+// one materialising Pauli pass when something next reads the amplitudes.  gates: the caller's
+// list (ops[i] is gates[i] lowered; kind < 0: ignored by the reference gate set); nch channels.
+void run_frames(qsim_batch* b, const qsim_gate* gates, const std::vector<Op>& ops, size_t nch) {
+    const size_t count = ops.size();
+    // a carried frame must be propagated (Cliffords) and conjugated (the rest) like noise
+    const bool noisy = (nch > 0 || b->frame_pending) && count > 0;
+    std::vector<Op> fops;
+    std::vector<StepClifford> cl(count, StepClifford{CL_NONE, 0, -1, 0});
+    for (size_t i = 0; i < count; ++i) {
+        if (ops[i].kind < 0) continue;
+        const qsim_gate g = map_gate(b, gates[i]);
+        static const int code_of[QSIM_GATE_COUNT] = {
+            CL_X, CL_Y, CL_Z, CL_H, CL_S, CL_NONE /*T*/, CL_SDG, CL_NONE /*Tdag*/,
+            CL_NONE, CL_NONE, CL_NONE /*Rx Ry Rz*/, CL_CNOT, CL_CZ, CL_NONE, CL_NONE /*CRY CRZ*/,
+            CL_SWAP, CL_NONE /*Toffoli*/};
+        cl[i] = StepClifford{code_of[g.type], g.qubits[0], g.nqubits > 1 ? g.qubits[1] : -1, 0};
+        fops.push_back(ops[i]);
+        // circuit step = frame index for ops conjugated by the frame; Clifford gates move the
+        // frame instead and run unconjugated (src -1)
+        fops.back().src = (noisy && cl[i].code == CL_NONE) ? (int)i : -1;
+    }
+    if (noisy) build_frames(b, count, nch, cl);
+    if (!fops.empty()) {
+        // every control is a tile bit; circuit-specialised kernels for the passes no frame
+        // conjugation reaches (all of them for a Clifford circuit)
+        const CtrlOutOff ctrl_off;
+        run_planned(b, fops, noisy ? b->d_frames : nullptr, nullptr);
+    }
+    if (noisy) {
+        if (nch > 0) b->step += count;
+        b->frame_pending = true;  // materialised by the next reader (or composed by the next run)
+    }
+}
+// One launch per gate over all trajectories; after each, this step's Pauli string per trajectory
+// (nch channels in d_ch) drawn and applied.
+void run_per_gate(qsim_batch* b, const std::vector<Op>& ops, size_t nch) {
+    for (const Op& op : ops) {
+        if (op.kind >= 0) launch_op(b->d, b->n, (uint64_t)b->batch, op, b->stream, &b->timer);
+        if (nch == 0) continue;
+        {
+            TimedLaunch tl(&b->timer, "pauli_draw", 0.0, b->stream);
+            hipLaunchKernelGGL(k_pauli_draw, dim3((b->batch + 255) / 256), dim3(256), 0, b->stream, b->d_ch, (int)nch,
+                               b->seed, b->step, b->batch, b->traj0, b->d_xz, b->d_e);
+            QSIM_HIPCHK(hipGetLastError());
+        }
+        ++b->step;
+        apply_frames(b);
+    }
 }
 }  // namespace
 
@@ -606,16 +687,9 @@ int qsim_batch_run_sweep(qsim_batch* b, const qsim_gate* gates, size_t count, co
         if (fused_path && b->basis && b->perm.empty()) {
             // first fused run of |0..0> members: the layout qsim_batch_run would choose for the
             // placeholder circuit (the same rule, memoised under the same kind)
-            int eff = b->n;
-            while ((1ll << (eff - b->n)) < (long long)b->batch) ++eff;
-            if (relabel_enabled(eff)) {
-                auto lower_under = [&](const std::vector<int>& pi) { return sweep_lower(b->n, pg, pi, false); };
-                const CtrlOutOff ctrl_off;
-                if (!layout_memo_get(b->n, 1, pg.data(), count * sizeof(qsim_gate), b->perm)) {
-                    b->perm = choose_layout(b->n, lower_under, relabel_tries()).perm;
-                    layout_memo_put(b->n, 1, pg.data(), count * sizeof(qsim_gate), b->perm);
-                }
-            }
+            const CtrlOutOff ctrl_off;
+            choose_first_layout(b, 1, pg.data(), count * sizeof(qsim_gate),
+                                [&](const std::vector<int>& pi) { return sweep_lower(b->n, pg, pi, false); });
         }
         b->basis = false;
         const std::vector<Op> ops = sweep_lower(b->n, pg, b->perm, true);
@@ -627,27 +701,7 @@ int qsim_batch_run_sweep(qsim_batch* b, const qsim_gate* gates, size_t count, co
             return;
         }
         const CtrlOutOff ctrl_off;  // (every control is a tile bit, as in the Pauli-frame passes)
-        PlanCache::Entry& pe = b->plans.get(ops, b->n, b->stream);
-        const Plan& plan = pe.plan;
-        // circuit-specialised kernels only for the passes without a member-dependent op
-        std::vector<char> tabled(plan.passes.size());
-        bool any_plain = false;
-        for (size_t p = 0; p < plan.passes.size(); ++p) {
-            tabled[p] = pass_has_step_op(plan, p);
-            any_plain = any_plain || !tabled[p];
-        }
-        int eff = b->n;
-        while ((1ll << (eff - b->n)) < (long long)b->batch) ++eff;
-        const JitModule* jm = any_plain ? jit_for(pe.jit, plan, eff) : nullptr;
-        b->ops.upload(plan.ops.data(), plan.ops.size() * sizeof(TileOp), b->stream);
-        b->stages.upload(plan.stages.data(), plan.stages.size() * sizeof(Stage), b->stream);
-        launch_fused(b->d, b->n, B, plan, (const TileOp*)b->ops.ptr, (const Stage*)b->stages.ptr, b->stream,
-                     &b->timer, jm, nullptr, FusedRange(), d_tab);
-        b->last_passes = (int)plan.passes.size();
-        b->last_jit_passes = 0;
-        if (jm)
-            for (size_t p = 0; p < jm->fn.size() && p < tabled.size(); ++p)
-                b->last_jit_passes += jm->fn[p] != nullptr && !tabled[p];
+        run_planned(b, ops, nullptr, d_tab);
     });
     if (rc == QSIM_OK && plain) return qsim_batch_run(b, gates, count, nullptr, 0, flags);
     return rc;
@@ -748,40 +802,29 @@ int qsim_batch_run(qsim_batch* b, const qsim_gate* gates, size_t count,
         }
         for (size_t i = 0; i < count; ++i) validate_gate(gates[i], b->n);
         static const bool fused_env = env_switch("QSIM_BATCH_FUSED", true);
-        const bool fused_path = b->n >= 10 && fused_env && !(flags & QSIM_BATCH_PER_GATE) &&
-                                !(flags & QSIM_BATCH_REFERENCE_NOISE);
-        if (flags & QSIM_BATCH_REFERENCE_NOISE) canonicalize(b);  // per-pair draws name positions
-        const bool frame_path = fused_path && b->n >= 10;  // (as the branch below)
+        const bool reference_noise = (flags & QSIM_BATCH_REFERENCE_NOISE) != 0;
+        const bool fused_path = b->n >= 10 && fused_env && !(flags & QSIM_BATCH_PER_GATE) && !reference_noise;
+        if (reference_noise) canonicalize(b);  // per-pair draws name positions
+        const bool frame_path = fused_path && b->n >= 10;  // (the Pauli-frame passes below)
         if (!frame_path) materialize(b);  // per-gate paths act on the plain vectors
+        auto reference_gate = [](const qsim_gate& g) { return g.type <= QSIM_GATE_H || g.type == QSIM_GATE_CNOT; };
         if (fused_path && b->basis && b->perm.empty() && count > 0) {
-            // First fused run of |0..0> trajectories: relabel for the plan's tile layouts when
-            // the whole batch is HBM-sized (as the JIT threshold, it counts every trajectory).
-            int eff = b->n;
-            while ((1ll << (eff - b->n)) < (long long)b->batch) ++eff;
-            if (relabel_enabled(eff)) {
-                auto lower_under = [&](const std::vector<int>& pi) {
-                    std::vector<Op> lops;
-                    for (size_t i = 0; i < count; ++i) {
-                        qsim_gate g = gates[i];
-                        if ((flags & QSIM_BATCH_REFERENCE_GATESET) &&
-                            !(g.type <= QSIM_GATE_H || g.type == QSIM_GATE_CNOT))
-                            continue;
-                        for (int j = 0; j < g.nqubits && j < 3; ++j) g.qubits[j] = pi[g.qubits[j]];
-                        lops.push_back(lower_gate(g, b->n));
-                        lops.back().src = -1;
-                    }
-                    return lops;
-                };
-                const int kind = 1 + (flags & QSIM_BATCH_REFERENCE_GATESET ? 1 : 0);
-                // (chosen under the tile-control rule the frame path plans with, and memoised
-                // under it)
-                std::unique_ptr<CtrlOutOff> ctrl_off;
-                if (frame_path) ctrl_off = std::make_unique<CtrlOutOff>();
-                if (!layout_memo_get(b->n, kind, gates, count * sizeof(qsim_gate), b->perm)) {
-                    b->perm = choose_layout(b->n, lower_under, relabel_tries()).perm;
-                    layout_memo_put(b->n, kind, gates, count * sizeof(qsim_gate), b->perm);
-                }
-            }
+            // First fused run of |0..0> trajectories: relabel for the plan's tile layouts (chosen
+            // under the tile-control rule the frame path plans with, and memoised under it)
+            std::unique_ptr<CtrlOutOff> ctrl_off;
+            if (frame_path) ctrl_off = std::make_unique<CtrlOutOff>();
+            choose_first_layout(b, 1 + (flags & QSIM_BATCH_REFERENCE_GATESET ? 1 : 0), gates, count * sizeof(qsim_gate),
+                                [&](const std::vector<int>& pi) {
+                                    std::vector<Op> lops;
+                                    for (size_t i = 0; i < count; ++i) {
+                                        qsim_gate g = gates[i];
+                                        if ((flags & QSIM_BATCH_REFERENCE_GATESET) && !reference_gate(g)) continue;
+                                        for (int j = 0; j < g.nqubits && j < 3; ++j) g.qubits[j] = pi[g.qubits[j]];
+                                        lops.push_back(lower_gate(g, b->n));
+                                        lops.back().src = -1;
+                                    }
+                                    return lops;
+                                });
         }
         b->basis = false;
         for (DevChannel& c : ch)
@@ -802,198 +845,22 @@ int qsim_batch_run(qsim_batch* b, const qsim_gate* gates, size_t count,
             const qsim_gate g = map_gate(b, gates[i]);
             if (flags & QSIM_BATCH_REFERENCE_GATESET) {
                 // src/NoiseModel.cu:742-763, 808-812, 821-825: only X/Y/Z/H and CNOT act.
-                const bool ok = g.type <= QSIM_GATE_H || g.type == QSIM_GATE_CNOT;
                 validate_gate(g, b->n);
-                ops.push_back(ok ? lower_gate(g, b->n) : Op{});
-                if (!ok) ops.back().kind = -1;
+                ops.push_back(reference_gate(g) ? lower_gate(g, b->n) : Op{});
+                if (!reference_gate(g)) ops.back().kind = -1;
             } else {
                 ops.push_back(lower_gate(g, b->n));
             }
         }
-        const uint64_t N = 1ull << b->n;
-        const uint64_t items_per_traj = N / 2 > 0 ? N / 2 : 1;
-        if (flags & QSIM_BATCH_REFERENCE_NOISE) {
-            // The reference's process (src/NoiseModel.cu:815-892): each gate, then for every
-            // Depolarizing channel entry (the only type batched mode applies, F5) one pass over
-            // all B x 2^(n-1) amplitude pairs; every pair draws its own uniform (counter hash of
-            // (seed, pass, global pair index) in place of its curandState) and, below p, a second
-            // one picks X / Y / Z at 1/3, 2/3 — applied to that pair only (F7).
+        if (reference_noise) {
             std::vector<NoiseChan> dep;
             for (size_t i = 0; i < n_channels; ++i)
                 if (channels[i].type == 0) dep.push_back(NoiseChan{0, channels[i].qubit, channels[i].probability});
-            if (pull_noise_supported(b->n, dep, false) && ensure_pull_buffers(b, dep.size())) {
-                // Pulled: the noise after gate i is applied by gate i+1's pass (out of place),
-                // the noise after the last gate by one identity pass; same draws, same states.
-                // The map of noise step i (codes set i & 1) is built on map_stream while the pass
-                // of step i - 1 runs; the pass of step i waits for it, the map of step i + 2
-                // waits for that pass (QSIM_NOISE_MAP_OVERLAP=0: one stream, one set in turn).
-                const char* oe = std::getenv("QSIM_NOISE_MAP_OVERLAP");
-                const bool overlap = oe == nullptr || std::atoi(oe) != 0;
-                const size_t G = ops.size();
-                auto codes_of = [&](size_t i) { return (void*)(b->d_codes + (i & 1) * b->codes_cap); };
-                const uint64_t c0 = b->ncounter;
-                b->ncounter += (uint64_t)G * dep.size();  // (one pass counter per channel entry, as the push path)
-                hipStream_t ms = overlap ? b->map_stream : b->stream;
-                auto map = [&](size_t i) {
-                    if (overlap && i >= 2) QSIM_HIPCHK(hipStreamWaitEvent(ms, b->ev_pull[i & 1], 0));
-                    launch_noise_map(b->n, (uint64_t)b->batch, b->traj0, dep, b->seed, c0 + i * dep.size(), codes_of(i), ms,
-                                     &b->timer);
-                    if (overlap) QSIM_HIPCHK(hipEventRecord(b->ev_map[i & 1], ms));
-                };
-                if (overlap) {  // (the previous run's passes may still read both sets)
-                    QSIM_HIPCHK(hipEventRecord(b->ev_start, b->stream));
-                    QSIM_HIPCHK(hipStreamWaitEvent(ms, b->ev_start, 0));
-                    for (size_t i = 0; i < std::min<size_t>(G, 2); ++i) map(i);
-                }
-                if (G && ops[0].kind >= 0) launch_op(b->d, b->n, (uint64_t)b->batch, ops[0], b->stream, &b->timer);
-                for (size_t i = 0; i < G; ++i) {
-                    if (overlap) {
-                        QSIM_HIPCHK(hipStreamWaitEvent(b->stream, b->ev_map[i & 1], 0));
-                    } else {
-                        map(i);
-                    }
-                    const Op* op = i + 1 < G && ops[i + 1].kind >= 0 ? &ops[i + 1] : nullptr;
-                    double2* dst = b->d == b->d0 ? b->d1 : b->d0;
-                    launch_pull_gate(b->d, dst, b->n, (uint64_t)b->batch, dep, op, codes_of(i), b->stream,
-                                     &b->timer);
-                    b->d = dst;
-                    if (overlap && i + 2 < G) {
-                        QSIM_HIPCHK(hipEventRecord(b->ev_pull[i & 1], b->stream));
-                        map(i + 2);
-                    }
-                }
-                if (b->pinned) settle_in_d0(b);
-                return;
-            }
-            bool all_tile = !ops.empty();
-            for (const Op& op : ops) all_tile = all_tile && gate_noise_tile_supported(b->n, op.kind >= 0 ? &op : nullptr);
-            if (all_tile) {
-                // noise.hip: gate + in-tile channels in LDS per step, each step's flip lists built on
-                // map_stream during the step before (when the device has room for them)
-                const size_t lb = gate_noise_lists_bytes(b->n, (uint64_t)b->batch, dep);
-                GnLists L{};
-                const bool lists = lb && ensure_list_buffers(b, lb);
-                if (lists) {
-                    L.buf[0] = b->d_lists;
-                    L.buf[1] = b->d_lists + b->lists_cap;
-                    L.set_bytes = b->lists_cap;
-                    L.ms = b->map_stream;
-                    L.built[0] = b->ev_map[0];
-                    L.built[1] = b->ev_map[1];
-                    L.used[0] = b->ev_pull[0];
-                    L.used[1] = b->ev_pull[1];
-                    L.start = b->ev_start;
-                }
-                // two trajectory halves on two streams (QSIM_NOISE_SPLIT, read per run; default 2):
-                // one half's tile pass overlaps the other's DRAM-random suffix push — W-BATCH config 4
-                // 57.8 -> 54.1 ms per step (3 parts 62.5, 4 parts 58.6)
-                const char* se = std::getenv("QSIM_NOISE_SPLIT");
-                const int k = se ? std::max(1, std::min(4, std::atoi(se))) : 2;
-                if (k > 1 && b->batch >= k && lists && split_tile_run(b, ops, dep, k, L)) return;
-                launch_gate_noise_run(b->d, b->n, (uint64_t)b->batch, b->traj0, ops, dep, b->seed, b->ncounter,
-                                      b->stream, &b->timer, lists ? &L : nullptr);
-                return;
-            }
-            for (const Op& op : ops) {
-                const Op* o = op.kind >= 0 ? &op : nullptr;
-                if (gate_noise_tile_supported(b->n, o)) {  // (noise.hip: gate + in-tile channels in LDS)
-                    launch_gate_noise_step(b->d, b->n, (uint64_t)b->batch, b->traj0, o, dep, b->seed, b->ncounter,
-                                           b->stream, &b->timer);
-                    continue;
-                }
-                if (o) launch_op(b->d, b->n, (uint64_t)b->batch, op, b->stream, &b->timer);
-                launch_noise_after_gate(b->d, b->n, dep, b->seed, b->ncounter, b->stream, &b->timer,
-                                        (uint64_t)b->batch, b->traj0);
-            }
-            return;
-        }
-        if (b->n >= 10 && fused_env && !(flags & QSIM_BATCH_PER_GATE)) {
-            // Fused tile passes over all trajectories (a tile never straddles two).  Noise is
-            // carried as per-trajectory Pauli frames: no noise kernel per gate, one frame build
-            // before and one materialising Pauli pass after the circuit.
-            // a carried frame must be propagated (Cliffords) and conjugated (the rest) like noise
-            const bool noisy = (!ch.empty() || b->frame_pending) && count > 0;
-            std::vector<Op> fops;
-            std::vector<StepClifford> cl(count, StepClifford{CL_NONE, 0, -1, 0});
-            for (size_t i = 0; i < ops.size(); ++i) {
-                if (ops[i].kind < 0) continue;  // ignored by the reference gate set
-                const qsim_gate g = map_gate(b, gates[i]);
-                static const int code_of[QSIM_GATE_COUNT] = {
-                    CL_X, CL_Y, CL_Z, CL_H, CL_S, CL_NONE /*T*/, CL_SDG, CL_NONE /*Tdag*/,
-                    CL_NONE, CL_NONE, CL_NONE /*Rx Ry Rz*/, CL_CNOT, CL_CZ, CL_NONE, CL_NONE /*CRY CRZ*/,
-                    CL_SWAP, CL_NONE /*Toffoli*/};
-                cl[i] = StepClifford{code_of[g.type], g.qubits[0], g.nqubits > 1 ? g.qubits[1] : -1, 0};
-                fops.push_back(ops[i]);
-                // circuit step = frame index for ops conjugated by the frame; Clifford gates move
-                // the frame instead and run unconjugated (src -1)
-                fops.back().src = (noisy && cl[i].code == CL_NONE) ? (int)i : -1;
-            }
-            if (noisy) {
-                const size_t need_frames = 2 * count * (size_t)b->batch;
-                if (need_frames > b->frames_cap) {
-                    QSIM_HIPCHK(hipStreamSynchronize(b->stream));
-                    if (b->d_frames) QSIM_HIPCHK(hipFree(b->d_frames));
-                    if (b->d_fe) QSIM_HIPCHK(hipFree(b->d_fe));
-                    b->d_frames = nullptr;
-                    b->d_fe = nullptr;
-                    QSIM_HIPCHK(hipMalloc((void**)&b->d_frames, need_frames * sizeof(uint64_t)));
-                    QSIM_HIPCHK(hipMalloc((void**)&b->d_fe, need_frames / 2 * sizeof(int)));
-                    b->frames_cap = need_frames;
-                }
-                TimedLaunch tl(&b->timer, "pauli_frames", 0.0, b->stream);
-                const uint64_t draws = (uint64_t)count * b->batch;
-                hipLaunchKernelGGL(k_draw_steps, dim3((unsigned)((draws + 255) / 256)), dim3(256), 0,
-                                   b->stream, b->d_ch, (int)ch.size(), b->seed, b->step, (int)count,
-                                   b->batch, b->traj0, b->d_frames, b->d_fe);
-                b->cliff.upload(cl.data(), cl.size() * sizeof(StepClifford), b->stream);
-                hipLaunchKernelGGL(k_frame_build, dim3((b->batch + 63) / 64), dim3(64), 0, b->stream,
-                                   (int)count, b->batch, b->d_frames, b->d_fe,
-                                   (const StepClifford*)b->cliff.ptr, b->d_xz, b->d_e, b->frame_pending ? 1 : 0);
-                QSIM_HIPCHK(hipGetLastError());
-            }
-            if (!fops.empty()) {
-                const CtrlOutOff ctrl_off;  // (Pauli-frame passes: every control is a tile bit)
-                PlanCache::Entry& pe = b->plans.get(fops, b->n, b->stream);
-                const Plan& plan = pe.plan;
-                // circuit-specialised kernels for the passes no frame conjugation reaches (all of
-                // them for a Clifford circuit); the JIT threshold counts the whole batch
-                int eff = b->n;
-                while ((1ll << (eff - b->n)) < (long long)b->batch) ++eff;
-                const JitModule* jm = jit_for(pe.jit, plan, eff);
-                b->ops.upload(plan.ops.data(), plan.ops.size() * sizeof(TileOp), b->stream);
-                b->stages.upload(plan.stages.data(), plan.stages.size() * sizeof(Stage), b->stream);
-                launch_fused(b->d, b->n, (uint64_t)b->batch, plan, (const TileOp*)b->ops.ptr,
-                             (const Stage*)b->stages.ptr, b->stream, &b->timer, jm,
-                             noisy ? b->d_frames : nullptr);
-                b->last_passes = (int)plan.passes.size();
-                b->last_jit_passes = 0;
-                if (jm)
-                    for (hipFunction_t f : jm->fn) b->last_jit_passes += f != nullptr;
-            }
-            if (noisy) {
-                if (!ch.empty()) b->step += count;
-                b->frame_pending = true;  // materialised by the next reader (or composed by the next run)
-            }
-            return;
-        }
-        for (const Op& op : ops) {
-            if (op.kind >= 0) launch_op(b->d, b->n, (uint64_t)b->batch, op, b->stream, &b->timer);
-            if (!ch.empty()) {
-                {
-                    TimedLaunch tl(&b->timer, "pauli_draw", 0.0, b->stream);
-                    hipLaunchKernelGGL(k_pauli_draw, dim3((b->batch + 255) / 256), dim3(256), 0,
-                                       b->stream, b->d_ch, (int)ch.size(), b->seed, b->step,
-                                       b->batch, b->traj0, b->d_xz, b->d_e);
-                    QSIM_HIPCHK(hipGetLastError());
-                }
-                ++b->step;
-                const uint64_t total = items_per_traj * (uint64_t)b->batch;
-                TimedLaunch tl(&b->timer, "pauli_apply", 0.0, b->stream);
-                hipLaunchKernelGGL(k_pauli_apply, dim3((unsigned)((total + 255) / 256)), dim3(256),
-                                   0, b->stream, b->d, b->n, b->d_xz, b->d_e, items_per_traj,
-                                   (uint64_t)b->batch);
-                QSIM_HIPCHK(hipGetLastError());
-            }
+            run_reference_noise(b, ops, dep);
+        } else if (frame_path) {
+            run_frames(b, gates, ops, ch.size());
+        } else {
+            run_per_gate(b, ops, ch.size());
         }
     });
 }

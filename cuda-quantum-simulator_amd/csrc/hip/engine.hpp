@@ -484,6 +484,44 @@ struct GnLists {
     hipStream_t ms;
     hipEvent_t built[2], used[2], start;
 };
+// Optional device blocks (a second 2^n buffer, code words, flip lists) are allocated only while
+// the device keeps this much free beside them; a caller that is refused takes its in-place path.
+constexpr size_t kAltMarginBytes = 256ull << 20;
+size_t device_free_bytes();                // 0 when it cannot be read (the HIP error is cleared)
+void* device_alloc_or_null(size_t bytes);  // null: the allocation failed (the HIP error is cleared)
+// The block, when the device has `bytes + beside` free and the allocation succeeds; else null.
+void* device_alloc_beside(size_t bytes, size_t beside);
+// What a noisy run keeps beside the amplitudes for the pulled and in-tile schedules: the side
+// stream their maps and lists are built on one or two steps ahead, its events, two sets of flip
+// lists and two sets of code words.  Owned by a state, an ensemble, or one part of a split
+// ensemble; nothing exists until the first run that needs it.
+struct NoiseSide {
+    hipStream_t stream = nullptr;
+    hipEvent_t built[2] = {}, used[2] = {}, start = nullptr;
+    char* lists = nullptr;
+    size_t lists_cap = 0;  // bytes of ONE set
+    unsigned char* codes = nullptr;
+    size_t codes_cap = 0;  // bytes of ONE set
+    NoiseSide() = default;
+    NoiseSide(const NoiseSide&) = delete;
+    NoiseSide& operator=(const NoiseSide&) = delete;
+    // The stream and its events, once (low_priority: at the device's lowest stream priority).
+    void ensure_stream(bool low_priority);
+    // Two sets of `bytes` each; grow only (the old block is freed once `main` and the side stream
+    // are idle).  false: the device has not 2 * bytes + kAltMarginBytes free, or refused.
+    bool ensure_lists(size_t bytes, hipStream_t main);
+    // Likewise (freed once `main` is idle: its passes are the words' last readers).  Whether the
+    // device has room is the caller's rule; false: the allocation failed.
+    bool ensure_codes(size_t bytes, hipStream_t main);
+    void* words(size_t step) const { return codes + (step & 1) * codes_cap; }
+    GnLists view() const;
+    void release_lists();  // (the caller has synchronised every stream that used them)
+    void release_codes();
+    // Waits for the side stream, then drops everything; the owner calls it before it destroys the
+    // main stream.
+    void destroy() noexcept;
+    ~NoiseSide() { destroy(); }
+};
 size_t gate_noise_lists_bytes(int n, uint64_t batch, const std::vector<NoiseChan>& chans);
 void launch_gate_noise_run(double2* st, int n, uint64_t batch, uint64_t traj0, const std::vector<Op>& ops,
                            const std::vector<NoiseChan>& chans, uint64_t seed, uint64_t& counter, hipStream_t s,
@@ -511,6 +549,17 @@ struct PullMapNext {
 };
 void launch_pull_gate(const double2* src, double2* dst, int n, uint64_t batch, const std::vector<NoiseChan>& chans,
                       const Op* op, const void* words, hipStream_t s, Timer* tm, const PullMapNext* next = nullptr);
+// A whole pulled run of gate steps (ops[i].kind < 0: no gate): the first gate in place, then the
+// noise after gate i and gate i + 1 in one pass out of place, the last noise step by an identity
+// pass.  buf[cur] holds the amplitudes; the passes alternate between the two buffers; returns which
+// one holds the result.  Step i's passes count from counter0 + i * chans.size().  overlap: the
+// words of step i (set i & 1 of side.codes) are built on side.stream while the pass of step i - 1
+// runs — the pass waits for them, the words of step i + 2 for that pass, the first two for whatever
+// ran on `s` before; else every map on `s` right before its pass.  side: codes for these channels
+// and (overlap) the stream are ensured by the caller.
+int launch_pull_noise_run(double2* const buf[2], int cur, int n, uint64_t batch, uint64_t traj0,
+                          const std::vector<Op>& ops, const std::vector<NoiseChan>& chans, uint64_t seed,
+                          uint64_t counter0, NoiseSide& side, hipStream_t s, Timer* tm, bool overlap);
 
 // Density matrices as 2n-index-bit states (density.hip).
 void dm_lower(int n, const qsim_gate* gates, size_t count, const qsim_noise_channel* ch,

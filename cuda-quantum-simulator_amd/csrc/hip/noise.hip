@@ -864,6 +864,87 @@ void launch_gate_noise_step(double2* st, int n, uint64_t batch, uint64_t traj0, 
     }
 }
 
+// ---------------------------------------------------------------------------------------
+// The side kit of the pulled and in-tile runs (engine.hpp NoiseSide)
+// ---------------------------------------------------------------------------------------
+size_t device_free_bytes() {
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return free_b;
+}
+void* device_alloc_or_null(size_t bytes) {
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) {
+        (void)hipGetLastError();  // (clear the sticky error: nothing the caller holds is broken)
+        return nullptr;
+    }
+    return p;
+}
+void* device_alloc_beside(size_t bytes, size_t beside) {
+    return device_free_bytes() < bytes + beside ? nullptr : device_alloc_or_null(bytes);
+}
+
+void NoiseSide::ensure_stream(bool low_priority) {
+    if (stream) return;
+    if (low_priority) {
+        int lo = 0, hi = 0;
+        QSIM_HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
+        QSIM_HIPCHK(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, lo));
+    } else {
+        QSIM_HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    }
+    for (hipEvent_t* e : {&built[0], &built[1], &used[0], &used[1], &start})
+        QSIM_HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+}
+bool NoiseSide::ensure_lists(size_t bytes, hipStream_t main) {
+    if (bytes <= lists_cap) return true;
+    if (lists) {
+        QSIM_HIPCHK(hipStreamSynchronize(main));
+        if (stream) QSIM_HIPCHK(hipStreamSynchronize(stream));
+        release_lists();
+    }
+    lists = (char*)device_alloc_beside(2 * bytes, kAltMarginBytes);
+    if (lists) lists_cap = bytes;
+    return lists != nullptr;
+}
+bool NoiseSide::ensure_codes(size_t bytes, hipStream_t main) {
+    if (bytes <= codes_cap) return true;
+    if (codes) {
+        QSIM_HIPCHK(hipStreamSynchronize(main));
+        release_codes();
+    }
+    codes = (unsigned char*)device_alloc_or_null(2 * bytes);
+    if (codes) codes_cap = bytes;
+    return codes != nullptr;
+}
+GnLists NoiseSide::view() const {
+    return GnLists{{lists, lists + lists_cap}, lists_cap, stream, {built[0], built[1]}, {used[0], used[1]}, start};
+}
+void NoiseSide::release_lists() {
+    if (lists) (void)hipFree(lists);
+    lists = nullptr;
+    lists_cap = 0;
+}
+void NoiseSide::release_codes() {
+    if (codes) (void)hipFree(codes);
+    codes = nullptr;
+    codes_cap = 0;
+}
+void NoiseSide::destroy() noexcept {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (hipEvent_t* e : {&built[0], &built[1], &used[0], &used[1], &start}) {
+        if (*e) (void)hipEventDestroy(*e);
+        *e = nullptr;
+    }
+    if (stream) (void)hipStreamDestroy(stream);
+    stream = nullptr;
+    release_codes();
+    release_lists();
+}
+
 // List capacity per (tile, channel) for the largest flip probability of `chans` (0: no lists —
 // above p ~ 0.1 the lists would outweigh the walks): mean 2048 P flips, cap = the power of two
 // >= mean + 6 sigma + 8 (p = 0.01: 64; P(overflow) ~ 1e-12 per list); a list that overflows is
@@ -1522,6 +1603,36 @@ void launch_pull_noise_step(const double2* src, double2* dst, int n, uint64_t ba
                             const Op* op, void* words, hipStream_t s, Timer* tm) {
     launch_noise_map(n, batch, traj0, chans, seed, counter0, words, s, tm);
     launch_pull_gate(src, dst, n, batch, chans, op, words, s, tm);
+}
+
+int launch_pull_noise_run(double2* const buf[2], int cur, int n, uint64_t batch, uint64_t traj0,
+                          const std::vector<Op>& ops, const std::vector<NoiseChan>& chans, uint64_t seed,
+                          uint64_t counter0, NoiseSide& side, hipStream_t s, Timer* tm, bool overlap) {
+    const size_t G = ops.size();
+    const hipStream_t ms = overlap ? side.stream : s;
+    auto gate = [&](size_t i) { return i < G && ops[i].kind >= 0 ? &ops[i] : nullptr; };
+    auto map = [&](size_t i) {
+        if (overlap && i >= 2) QSIM_HIPCHK(hipStreamWaitEvent(ms, side.used[i & 1], 0));
+        launch_noise_map(n, batch, traj0, chans, seed, counter0 + i * chans.size(), side.words(i), ms, tm);
+        if (overlap) QSIM_HIPCHK(hipEventRecord(side.built[i & 1], ms));
+    };
+    if (overlap) {  // (the previous run's passes may still read both sets)
+        QSIM_HIPCHK(hipEventRecord(side.start, s));
+        QSIM_HIPCHK(hipStreamWaitEvent(ms, side.start, 0));
+        for (size_t i = 0; i < std::min<size_t>(G, 2); ++i) map(i);
+    }
+    if (gate(0)) launch_op(buf[cur], n, batch, ops[0], s, tm);
+    for (size_t i = 0; i < G; ++i) {
+        if (overlap) QSIM_HIPCHK(hipStreamWaitEvent(s, side.built[i & 1], 0));
+        else map(i);
+        launch_pull_gate(buf[cur], buf[cur ^ 1], n, batch, chans, gate(i + 1), side.words(i), s, tm);
+        cur ^= 1;
+        if (overlap && i + 2 < G) {
+            QSIM_HIPCHK(hipEventRecord(side.used[i & 1], s));
+            map(i + 2);
+        }
+    }
+    return cur;
 }
 
 }  // namespace qsim_hip

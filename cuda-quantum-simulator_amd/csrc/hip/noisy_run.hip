@@ -1,6 +1,7 @@
 // noisy_run.hip — the noisy trajectory run on a single-GPU state (qsim_noisy_run, qsim_noise_apply):
-// which of noise.hip's paths a run takes (in-tile, pulled, pushed) and the buffers, side stream and
-// events the first two keep on the state.  The kernels and their launchers are noise.hip.
+// which of noise.hip's paths a run takes (in-tile, pulled, pushed) and the buffers the first two
+// keep on the state (its NoiseSide and the second 2^n buffer).  The kernels, their launchers and
+// the schedules of the in-tile and pulled runs are noise.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -11,77 +12,18 @@
 
 using namespace qsim_hip;
 
-// The noise side stream and its events (the pulled path's code-word maps, the in-tile path's lists).
-static void ensure_noise_stream(qsim_state* s) {
-    if (s->noise_stream) return;
-    QSIM_HIPCHK(hipStreamCreateWithFlags(&s->noise_stream, hipStreamNonBlocking));
-    for (hipEvent_t* e : {&s->nev_map[0], &s->nev_map[1], &s->nev_pull[0], &s->nev_pull[1], &s->nev_start})
-        QSIM_HIPCHK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-}
 // Buffers of the pulled noise path: the second state buffer, two sets of per-step code words.
 static bool ensure_noise_buffers(qsim_state* s, size_t nch) {
+    const size_t state_b = sizeof(double2) << s->n;
     const size_t codes_b = pull_noise_codes_bytes(s->n, 1, nch);
     // Allocate only when the device keeps room for another state of this size beside the new
     // buffers — the rule trim_noise_buffers keeps them by — so a device with between one and two
     // states of room runs the push kernels instead of allocating and freeing a second state on
     // every run.
-    const size_t need = (s->alt ? 0 : (sizeof(double2) << s->n)) + (codes_b > s->noise_codes_cap ? 2 * codes_b : 0);
-    if (need) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (free_b < need + (sizeof(double2) << s->n) + kAltMarginBytes) return false;
-    }
-    if (!ensure_alt(s)) return false;
-    auto grab = [&](unsigned char** p, size_t bytes) {
-        if (hipMalloc((void**)p, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            *p = nullptr;
-            return false;
-        }
-        return true;
-    };
-    if (codes_b > s->noise_codes_cap) {
-        if (s->noise_codes) {
-            QSIM_HIPCHK(hipStreamSynchronize(s->stream));
-            (void)hipFree(s->noise_codes);
-            s->noise_codes = nullptr;
-            s->noise_codes_cap = 0;
-        }
-        if (!grab(&s->noise_codes, 2 * codes_b)) return false;
-        s->noise_codes_cap = codes_b;
-    }
-    ensure_noise_stream(s);
-    return true;
-}
-
-// Two sets of the in-tile path's flip lists, when they fit beside a margin (false: the tile
-// kernels walk the draws themselves).
-static bool ensure_noise_lists(qsim_state* s, size_t bytes) {
-    if (bytes > s->noise_lists_cap) {
-        if (s->noise_lists) {
-            QSIM_HIPCHK(hipStreamSynchronize(s->stream));
-            if (s->noise_stream) QSIM_HIPCHK(hipStreamSynchronize(s->noise_stream));
-            (void)hipFree(s->noise_lists);
-            s->noise_lists = nullptr;
-            s->noise_lists_cap = 0;
-        }
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        if (free_b < 2 * bytes + kAltMarginBytes) return false;
-        if (hipMalloc((void**)&s->noise_lists, 2 * bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            s->noise_lists = nullptr;
-            return false;
-        }
-        s->noise_lists_cap = bytes;
-    }
-    ensure_noise_stream(s);
+    const size_t need = (s->alt ? 0 : state_b) + (codes_b > s->noise.codes_cap ? 2 * codes_b : 0);
+    if (need && device_free_bytes() < need + state_b + kAltMarginBytes) return false;
+    if (!ensure_alt(s) || !s->noise.ensure_codes(codes_b, s->stream)) return false;
+    s->noise.ensure_stream(false);
     return true;
 }
 
@@ -91,23 +33,87 @@ static void trim_noise_buffers(qsim_state* s) {
     // QSIM_NOISE_KEEP_BUFFERS: 1 always keep, 0 always free (tests)
     static const int keep = env_int("QSIM_NOISE_KEEP_BUFFERS", -1);
     if (keep == 1) return;
-    if (keep != 0) {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-            (void)hipGetLastError();
-            free_b = 0;
-        }
-        if (free_b >= (sizeof(double2) << s->n) + kAltMarginBytes) return;
-    }
+    if (keep != 0 && device_free_bytes() >= (sizeof(double2) << s->n) + kAltMarginBytes) return;
     QSIM_HIPCHK(hipStreamSynchronize(s->stream));
-    if (s->noise_stream) QSIM_HIPCHK(hipStreamSynchronize(s->noise_stream));
-    if (s->noise_codes) (void)hipFree(s->noise_codes);
-    s->noise_codes = nullptr;
-    s->noise_codes_cap = 0;
-    if (s->noise_lists) (void)hipFree(s->noise_lists);
-    s->noise_lists = nullptr;
-    s->noise_lists_cap = 0;
+    if (s->noise.stream) QSIM_HIPCHK(hipStreamSynchronize(s->noise.stream));
+    s->noise.release_codes();
+    s->noise.release_lists();
     if (!s->relayout) release_alt(s);
+}
+
+// QSIM_NOISY_TILE=1 (from 12 qubits, flip-only models): the in-tile path (noise.hip
+// launch_gate_noise_run: the gate and the channel prefix whose qubits lie in its tile in one LDS
+// pass, their flips from lists built one step ahead on the side stream — two sets, when they fit
+// beside a margin, else the tile kernels walk the draws themselves — the rest pushed one launch
+// per channel): the same draws, so the same states as the pulled and pushed paths.  Opt-in: at 26
+// qubits with 26 channels the 14-15 per-channel suffix launches (0.04 ms each) outweigh the pull
+// pass, 904 vs 1 024 gates/s.  false: not this run (nothing launched).
+static bool run_tile(qsim_state* s, const std::vector<Op>& ops, const std::vector<NoiseChan>& chans, uint64_t seed,
+                     uint64_t* counter) {
+    bool tile = env_switch("QSIM_NOISY_TILE", false) && s->n >= 12;  // (read per run: tests switch it)
+    for (const NoiseChan& ch : chans) tile = tile && (ch.type == 0 || ch.type >= 3);
+    for (const Op& op : ops) tile = tile && gate_noise_tile_supported(s->n, &op);
+    if (!tile) return false;
+    const size_t lb = gate_noise_lists_bytes(s->n, 1, chans);
+    GnLists L{};
+    const bool lists = lb && s->noise.ensure_lists(lb, s->stream);
+    if (lists) {
+        s->noise.ensure_stream(false);
+        L = s->noise.view();
+    }
+    launch_gate_noise_run(s->d, s->n, 1, 0, ops, chans, seed, *counter, s->stream, &s->timer, lists ? &L : nullptr);
+    trim_noise_buffers(s);
+    return true;
+}
+
+// QSIM_NOISE_MAP_FUSED=1 (opt-in): step i's pass also builds step i + 1's words (its hash-and-log
+// walks meant to fill its own memory stalls; noise.hip k_pull_gate<..., MAP>), one stream.
+// Measured slower at 26 qubits: 1.22 ms per fused pass against 0.70 + 0.24 ms apart, 815 vs 1 063
+// gates/s (the walks and their LDS cost the pass its occupancy), so the default is the word map as
+// a kernel of its own, beside the pass (overlap) or before it (launch_pull_noise_run).
+static void run_pulled_map_fused(qsim_state* s, const std::vector<Op>& ops, const std::vector<NoiseChan>& chans,
+                                 uint64_t seed, uint64_t c0) {
+    const size_t G = ops.size();
+    launch_noise_map(s->n, 1, 0, chans, seed, c0, s->noise.words(0), s->stream, &s->timer);
+    launch_op(s->d, s->n, 1, ops[0], s->stream, &s->timer);
+    for (size_t i = 0; i < G; ++i) {
+        const PullMapNext nx{0, seed, c0 + (i + 1) * chans.size(), s->noise.words(i + 1)};
+        launch_pull_gate(s->d, s->alt, s->n, 1, chans, i + 1 < G ? &ops[i + 1] : nullptr, s->noise.words(i),
+                         s->stream, &s->timer, i + 1 < G ? &nx : nullptr);
+        std::swap(s->d, s->alt);
+    }
+}
+
+// Flip channels only: the noise after gate i is applied by gate i+1's pass (out of place), the
+// noise after the last gate by one identity pass (noise.hip); the same draws as the per-channel
+// passes, so the same state.  false: not this run (nothing launched).
+static bool run_pulled(qsim_state* s, const std::vector<Op>& ops, const std::vector<NoiseChan>& chans, uint64_t seed,
+                       uint64_t* counter) {
+    if (!pull_noise_supported(s->n, chans, true) || !ensure_noise_buffers(s, chans.size())) return false;
+    // where the amplitudes are now: a pinned state's handed-out pointer (prep() leaves the
+    // amplitudes of a pinned state in the buffer that was handed out, which may be either one)
+    double2* const home = s->d;
+    // QSIM_NOISE_MAP_OVERLAP=0: the word maps on the state's stream (read per run, as the next
+    // one: tests switch them)
+    const bool overlap = env_switch("QSIM_NOISE_MAP_OVERLAP", true);
+    const uint64_t c0 = *counter;
+    *counter += (uint64_t)ops.size() * chans.size();
+    if (env_switch("QSIM_NOISE_MAP_FUSED", false) && !ops.empty()) {
+        run_pulled_map_fused(s, ops, chans, seed, c0);
+    } else {
+        double2* const buf[2] = {s->d, s->alt};
+        const int at = launch_pull_noise_run(buf, 0, s->n, 1, 0, ops, chans, seed, c0, s->noise, s->stream, &s->timer,
+                                             overlap);
+        s->d = buf[at];
+        s->alt = buf[at ^ 1];
+    }
+    settle_home(s, home);
+    // The second buffer and the code words stay for the next run (qsim_state_memory_bytes counts
+    // them) only while the device keeps room for another state of this size beside them;
+    // otherwise they are freed now, so a later StateVector does not fail where the reference's
+    // single-buffer one would not.
+    trim_noise_buffers(s);
+    return true;
 }
 
 extern "C" {
@@ -147,106 +153,7 @@ int qsim_noisy_run(qsim_state* s, const qsim_gate* gates, size_t count,
         std::vector<NoiseChan> chans;
         for (size_t c = 0; c < n_channels; ++c)
             chans.push_back(NoiseChan{channels[c].type, channels[c].qubit, channels[c].probability});
-        // where the amplitudes are now: a pinned state's handed-out pointer (prep() leaves the
-        // amplitudes of a pinned state in the buffer that was handed out, which may be either one)
-        double2* const home = s->d;
-        // QSIM_NOISY_TILE=1 (from 12 qubits, flip-only models): the in-tile path (noise.hip
-        // launch_gate_noise_run: the gate and the channel prefix whose qubits lie in its tile in one
-        // LDS pass, their flips from lists built one step ahead on noise_stream, the rest pushed one
-        // launch per channel) — the same draws, so the same states as the pulled and pushed paths.
-        // Opt-in: at 26 qubits with 26 channels the 14-15 per-channel suffix launches (0.04 ms
-        // each) outweigh the pull pass, 904 vs 1 024 gates/s.
-        {
-            bool tile = env_switch("QSIM_NOISY_TILE", false) && s->n >= 12;  // (read per run: tests switch it)
-            for (const NoiseChan& ch : chans) tile = tile && (ch.type == 0 || ch.type >= 3);
-            for (const Op& op : ops) tile = tile && gate_noise_tile_supported(s->n, &op);
-            if (tile) {
-                const size_t lb = gate_noise_lists_bytes(s->n, 1, chans);
-                GnLists L{};
-                const bool lists = lb && ensure_noise_lists(s, lb);
-                if (lists) {
-                    L.buf[0] = s->noise_lists;
-                    L.buf[1] = s->noise_lists + s->noise_lists_cap;
-                    L.set_bytes = s->noise_lists_cap;
-                    L.ms = s->noise_stream;
-                    L.built[0] = s->nev_map[0];
-                    L.built[1] = s->nev_map[1];
-                    L.used[0] = s->nev_pull[0];
-                    L.used[1] = s->nev_pull[1];
-                    L.start = s->nev_start;
-                }
-                launch_gate_noise_run(s->d, s->n, 1, 0, ops, chans, seed, *counter, s->stream, &s->timer,
-                                      lists ? &L : nullptr);
-                trim_noise_buffers(s);
-                return;
-            }
-        }
-        if (pull_noise_supported(s->n, chans, true) && ensure_noise_buffers(s, chans.size())) {
-            // Flip channels only: the noise after gate i is applied by gate i+1's pass (out of
-            // place), the noise after the last gate by one identity pass (noise.hip); the same
-            // draws as the per-channel passes below, so the same state.
-            // The words of step i (set i & 1) are built on noise_stream while the pass of step
-            // i - 1 runs; the pass of step i waits for them, the words of step i + 2 for that pass
-            // (QSIM_NOISE_MAP_OVERLAP=0: one stream; read per run, as the next one: tests switch them).
-            const bool overlap = env_switch("QSIM_NOISE_MAP_OVERLAP", true);
-            const size_t G = ops.size();
-            const uint64_t c0 = *counter;
-            *counter += (uint64_t)G * n_channels;
-            auto words = [&](size_t i) { return (void*)(s->noise_codes + (i & 1) * s->noise_codes_cap); };
-            // QSIM_NOISE_MAP_FUSED=1 (opt-in): step i's pass also builds step i + 1's words (its
-            // hash-and-log walks meant to fill its own memory stalls; noise.hip k_pull_gate<...,
-            // MAP>), one stream.  Measured slower at 26 qubits: 1.22 ms per fused pass against
-            // 0.70 + 0.24 ms apart, 815 vs 1 063 gates/s (the walks and their LDS cost the pass its
-            // occupancy), so the default is the word map as a kernel of its own, beside the pass
-            // (overlap) or before it.
-            if (env_switch("QSIM_NOISE_MAP_FUSED", false) && G) {
-                launch_noise_map(s->n, 1, 0, chans, seed, c0, words(0), s->stream, &s->timer);
-                launch_op(s->d, s->n, 1, ops[0], s->stream, &s->timer);
-                for (size_t i = 0; i < G; ++i) {
-                    double2* dst = s->alt;
-                    const PullMapNext nx{0, seed, c0 + (i + 1) * n_channels, words(i + 1)};
-                    launch_pull_gate(s->d, dst, s->n, 1, chans, i + 1 < G ? &ops[i + 1] : nullptr, words(i), s->stream,
-                                     &s->timer, i + 1 < G ? &nx : nullptr);
-                    s->alt = s->d;
-                    s->d = dst;
-                }
-                settle_home(s, home);
-                trim_noise_buffers(s);
-                return;
-            }
-            hipStream_t ms = overlap ? s->noise_stream : s->stream;
-            auto map = [&](size_t i) {
-                if (overlap && i >= 2) QSIM_HIPCHK(hipStreamWaitEvent(ms, s->nev_pull[i & 1], 0));
-                launch_noise_map(s->n, 1, 0, chans, seed, c0 + i * n_channels, words(i), ms, &s->timer);
-                if (overlap) QSIM_HIPCHK(hipEventRecord(s->nev_map[i & 1], ms));
-            };
-            if (overlap) {  // (the previous run's passes may still read both sets)
-                QSIM_HIPCHK(hipEventRecord(s->nev_start, s->stream));
-                QSIM_HIPCHK(hipStreamWaitEvent(ms, s->nev_start, 0));
-                for (size_t i = 0; i < std::min<size_t>(G, 2); ++i) map(i);
-            }
-            if (G) launch_op(s->d, s->n, 1, ops[0], s->stream, &s->timer);
-            for (size_t i = 0; i < G; ++i) {
-                if (overlap) QSIM_HIPCHK(hipStreamWaitEvent(s->stream, s->nev_map[i & 1], 0));
-                else map(i);
-                double2* dst = s->alt;
-                launch_pull_gate(s->d, dst, s->n, 1, chans, i + 1 < G ? &ops[i + 1] : nullptr, words(i), s->stream,
-                                 &s->timer);
-                s->alt = s->d;
-                s->d = dst;
-                if (overlap && i + 2 < G) {
-                    QSIM_HIPCHK(hipEventRecord(s->nev_pull[i & 1], s->stream));
-                    map(i + 2);
-                }
-            }
-            settle_home(s, home);
-            // The second buffer and the code words stay for the next run (qsim_state_memory_bytes
-            // counts them) only while the device keeps room for another state of this size beside
-            // them; otherwise they are freed now, so a later StateVector does not fail where the
-            // reference's single-buffer one would not.
-            trim_noise_buffers(s);
-            return;
-        }
+        if (run_tile(s, ops, chans, seed, counter) || run_pulled(s, ops, chans, seed, counter)) return;
         for (const Op& op : ops) {
             launch_op(s->d, s->n, 1, op, s->stream, &s->timer);
             for (size_t c = 0; c < n_channels; ++c)

@@ -157,17 +157,8 @@ bool ensure_alt(qsim_state* s) {
     static const bool off = env_switch("QSIM_RELAYOUT_NO_ALT", false);
     if (off) return false;
     const size_t bytes = sizeof(double2) << s->n;
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    if (free_b < bytes + kAltMarginBytes) return false;
-    void* p = nullptr;
-    if (hipMalloc(&p, bytes) != hipSuccess) {
-        (void)hipGetLastError();  // (clear the sticky error: the state itself is intact)
-        return false;
-    }
+    void* p = device_alloc_beside(bytes, kAltMarginBytes);
+    if (!p) return false;
     s->alt_base = p;
     s->alt = reinterpret_cast<double2*>(p);
     return true;
@@ -429,7 +420,7 @@ int qsim_state_memory_bytes(qsim_state* s, uint64_t* bytes) {
         QSIM_REQUIRE(bytes, QSIM_ERR_INVALID_ARGUMENT, "null out");
         const uint64_t amps = sizeof(double2) << s->n;
         *bytes = amps + (s->alt_base ? amps : 0) + 4096 * sizeof(double) + sizeof(double) + s->scratch.cap +
-                 s->ops.cap + s->stages.cap + s->expect_terms.cap + 2 * s->noise_codes_cap + 2 * s->noise_lists_cap;
+                 s->ops.cap + s->stages.cap + s->expect_terms.cap + 2 * s->noise.codes_cap + 2 * s->noise.lists_cap;
         if (s->grad)
             *bytes += 2 * amps + s->grad->out_cap * sizeof(double) + s->grad->ops.cap + s->grad->stages.cap +
                       s->grad->terms.cap;

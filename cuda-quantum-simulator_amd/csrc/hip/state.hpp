@@ -123,16 +123,9 @@ struct qsim_state {
     double2* alt = nullptr;
     double2* base_d = nullptr;  // the amplitudes' address inside `base` (d == base_d or alt_base)
     bool pinned = false;
-    // pulled noise (NoisySimulator flip channels, noise.hip): two sets of per-step code words
-    // (steps alternate), so the next step's words are built on noise_stream during this pass
-    unsigned char* noise_codes = nullptr;
-    size_t noise_codes_cap = 0;  // bytes of ONE set
-    // in-tile noise (noise.hip launch_gate_noise_run): two sets of per-step flip lists, built on
-    // noise_stream one step ahead
-    char* noise_lists = nullptr;
-    size_t noise_lists_cap = 0;  // bytes of ONE set
-    hipStream_t noise_stream = nullptr;
-    hipEvent_t nev_map[2] = {}, nev_pull[2] = {}, nev_start = nullptr;
+    // Noisy runs (noisy_run.hip): the side stream, events, flip lists and code words of the pulled
+    // (noise.hip launch_pull_noise_run) and in-tile (launch_gate_noise_run) schedules
+    qsim_hip::NoiseSide noise;
     std::unique_ptr<qsim_hip::GradWork> grad;  // adjoint gradients: work states and plans (null until used)
     // run sharing: the gate list of the last fused qsim_run (cleared by every reader and writer of
     // amplitudes in between), the cycle, and share_block (a caller that reads right after its run)
@@ -146,14 +139,9 @@ struct qsim_state {
     ~qsim_state() {
         if (stream) (void)hipStreamSynchronize(stream);
         grad.reset();
-        if (noise_stream) (void)hipStreamSynchronize(noise_stream);
-        for (hipEvent_t e : {nev_map[0], nev_map[1], nev_pull[0], nev_pull[1], nev_start})
-            if (e) (void)hipEventDestroy(e);
-        if (noise_stream) (void)hipStreamDestroy(noise_stream);
+        noise.destroy();
         if (base) (void)hipFree(base);
         if (alt_base) (void)hipFree(alt_base);
-        if (noise_codes) (void)hipFree(noise_codes);
-        if (noise_lists) (void)hipFree(noise_lists);
         if (d_partials) (void)hipFree(d_partials);
         if (d_result) (void)hipFree(d_result);
         if (stream) (void)hipStreamDestroy(stream);
@@ -182,8 +170,6 @@ void check_dm(const qsim_state* s, int n);  // s holds rho of n qubits (density.
 inline int state_tile_height(const qsim_state* s) { return s->tile_h >= 0 ? s->tile_h : tile_height_for(s->n); }
 
 // ---- the state core (state.hip) ---------------------------------------------------------------
-// A second 2^n buffer is allocated only while the device keeps this much free beside it.
-constexpr size_t kAltMarginBytes = 256ull << 20;
 bool ensure_alt(qsim_state* s);   // false: no room (or refused): the caller stays in place
 void release_alt(qsim_state* s);  // free the buffer the amplitudes are not in
 void canonicalize(qsim_state* s);      // undo the relabeling (flushes a run-sharing cycle first)

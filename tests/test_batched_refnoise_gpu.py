@@ -217,6 +217,127 @@ def test_pulled_noise_equals_push_16q(qsim, gpu_ready, monkeypatch):
     assert np.array_equal(np.stack([s.getStateVector(t) for t in (0, 63, 127)]), out[0])
 
 
+def _short_circuit(q, n, gates):
+    """`gates` gates on low, middle and top qubits; the S gates are ignored by the reference gate set."""
+    c = q.Circuit(n)
+    steps = [lambda: c.h(0), lambda: c.cnot(n - 1, 3), lambda: c.s(n - 2), lambda: c.x(n - 1), lambda: c.cnot(2, n - 1)]
+    for i in range(gates):
+        steps[i % len(steps)]()
+    return c
+
+
+@pytest.mark.parametrize("gates", [0, 1, 2, 3, 5])
+@pytest.mark.parametrize("refgates", [False, True])
+def test_pulled_run_gate_counts(qsim, oracle, gpu_ready, monkeypatch, gates, refgates):
+    """The edges of the pulled schedule (noise.hip launch_pull_noise_run) at the smallest size it
+    takes, 9 qubits, three trajectories: no gate (no pass), one (only the first set of words), two
+    (both sets, no reuse), three and five (a set reused once and twice; under the reference gate
+    set the third step has no gate); run twice on one object, so the second run starts behind the
+    first one's passes, on both code sets, and from whichever buffer the first one ended in.  Maps
+    on the side stream and on the object's own give the same bits, and the oracle's states."""
+    monkeypatch.setenv("QSIM_NOISE_PULL", "1")
+    n, B, seed = 9, 3, 13
+    c = _short_circuit(qsim, n, gates)
+    assert len(c.getGates()) == gates
+    nm = qsim.NoiseModel()
+    nm.addDepolarizingAll(n, 0.2)
+    entries = [(0, q, 0.2) for q in range(n)]
+    want, counter = None, 0
+    for _ in range(2):
+        want, counter = oracle.batched_reference_run(n, B, oracle.gates_of(c), entries, seed, refgates,
+                                                      states=want, counter=counter)
+    got = []
+    for overlap in ("1", "0"):
+        monkeypatch.setenv("QSIM_NOISE_MAP_OVERLAP", overlap)
+        s = qsim.BatchedSimulator(n, B, nm, noise=qsim.BatchedNoise.Reference,
+                                  gate_set=qsim.BatchedGateSet.Reference if refgates else qsim.BatchedGateSet.Full)
+        s.setSeed(seed)
+        s.run(c)
+        s.run(c)
+        got.append(np.stack([s.getStateVector(t) for t in range(B)]))
+        s.close()
+    assert np.array_equal(got[0], got[1])
+    np.testing.assert_allclose(got[0], want, atol=1e-12, rtol=0)
+
+
+def test_pinned_batch_pulled_run_with_odd_gate_count(qsim, oracle, gpu_ready, monkeypatch):
+    """A handed-out device pointer, then pulled runs of three and of five gates (each ends in the
+    second buffer): the result is copied back, so the pointer still addresses it."""
+    import ctypes
+    from qsim_amd import _lib
+    monkeypatch.setenv("QSIM_NOISE_PULL", "1")
+    n, B, seed = 9, 3, 14
+    nm = qsim.NoiseModel()
+    nm.addDepolarizingAll(n, 0.2)
+    entries = [(0, q, 0.2) for q in range(n)]
+    s = qsim.BatchedSimulator(n, B, nm, noise=qsim.BatchedNoise.Reference)
+    s.setSeed(seed)
+    ptr = ctypes.c_void_p()
+    _lib.check(_lib.hip.qsim_batch_device_ptr(s._h, ctypes.byref(ptr)))
+    want, counter = None, 0
+    for gates in (3, 5):
+        c = _short_circuit(qsim, n, gates)
+        s.run(c)
+        want, counter = oracle.batched_reference_run(n, B, oracle.gates_of(c), entries, seed, states=want,
+                                                      counter=counter)
+        s.synchronize()
+        hip = ctypes.CDLL("libamdhip64.so.7")
+        hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
+        at_ptr = np.empty((B, 1 << n), dtype=np.complex128)
+        assert hip.hipMemcpy(at_ptr.ctypes.data, ptr, at_ptr.nbytes, 2) == 0  # D2H
+        np.testing.assert_allclose(at_ptr, want, atol=1e-12, rtol=0)
+    again = ctypes.c_void_p()
+    _lib.check(_lib.hip.qsim_batch_device_ptr(s._h, ctypes.byref(again)))
+    assert again.value == ptr.value
+    np.testing.assert_allclose(np.stack([s.getStateVector(t) for t in range(B)]), want, atol=1e-12, rtol=0)
+
+
+def test_alternating_noise_paths_on_one_object(qsim, gpu_ready, monkeypatch):
+    """One object through pulled, in-tile (split in two parts), Pauli-frame and sweep runs, twice
+    round, so every run of the pulled and in-tile schedules meets the side stream, events and
+    buffers as a run of another kind left them: every member equals a fresh object taken through
+    the same sequence one launch per gate, with the push kernels for the reference noise."""
+    n, B, seed = 12, 4, 19
+    c = _circuit(qsim, n, 13, seed)
+    noisy = qsim.NoiseModel()
+    noisy.addDepolarizingAll(n, 0.03)  # (small enough for flip lists, noise.hip gn_list_cap)
+    slots = sum(1 for g in c.getGates() if g.type in (qsim.GateType.Rx, qsim.GateType.Ry, qsim.GateType.Rz))
+    assert slots > 0
+    angles = np.random.default_rng(seed).uniform(-3, 3, (B, slots))
+
+    def sequence(s, per_gate, rounds=2):
+        def reference(pull, tile):
+            monkeypatch.setenv("QSIM_NOISE_PULL", pull)
+            monkeypatch.setenv("QSIM_NOISE_TILE", tile)
+            s.setNoiseModel(noisy)
+            s.setNoiseSemantics(qsim.BatchedNoise.Reference)
+            s.run(c, per_gate=per_gate)
+        for _ in range(rounds):
+            reference("0" if per_gate else "1", "0")  # pulled
+            reference("0", "0" if per_gate else "1")  # in-tile
+            s.setNoiseSemantics(qsim.BatchedNoise.Physical)
+            s.run(c, per_gate=per_gate)  # Pauli frames
+            s.setNoiseModel(qsim.NoiseModel())
+            s.runSweep(c, angles, per_gate=per_gate)
+        return np.stack([s.getStateVector(t) for t in range(B)])
+
+    out = []
+    for per_gate in (False, True):
+        s = qsim.BatchedSimulator(n, B, noisy, noise=qsim.BatchedNoise.Physical)
+        s.setSeed(seed)
+        out.append(sequence(s, per_gate))
+        s.close()
+    np.testing.assert_allclose(out[0], out[1], atol=1e-12, rtol=0)
+    assert abs(np.sum(np.abs(out[0][B - 1]) ** 2) - 1.0) < 1e-10
+    # (one round on a profiled object: the sequence does take the four paths it names)
+    s = qsim.BatchedSimulator(n, B, noisy, noise=qsim.BatchedNoise.Physical)
+    s.profile(True)
+    sequence(s, False, rounds=1)
+    names = {k["name"] for k in s.profileStats()}
+    assert {"noise_map", "pull_gate", "noise_lists", "gate_noise", "pauli_frames"} <= names, names
+    assert s.lastRunInfo()[0] > 0  # (the sweep ran as fused passes)
+
+
 @pytest.mark.parametrize("n,B,seed,traj0", [(6, 5, 5, 3), (3, 50, 7, 3), (7, 9, 8, 1), (9, 6, 5, 2)])
 def test_one_launch_noise_accesses_stay_in_unit(qsim, oracle, gpu_ready, monkeypatch, n, B, seed, traj0):
     """the one-launch kernel (k_noise_units) run range-checked on the device

@@ -172,6 +172,43 @@ def test_pulled_flip_noise_matches_oracle(qsim, oracle, gpu_ready, monkeypatch, 
     np.testing.assert_allclose(sim.getStateVector(), want2, atol=1e-12, rtol=0)
 
 
+def _short_circuit(q, n, gates):
+    """`gates` gates on low, middle and top qubits (1-qubit, controlled, diagonal, SWAP)."""
+    c = q.Circuit(n)
+    steps = [lambda: c.h(0), lambda: c.cnot(n - 1, 3), lambda: c.rx(n - 2, 0.7), lambda: c.cz(1, n - 1),
+             lambda: c.swap(2, n - 1)]
+    for i in range(gates):
+        steps[i % len(steps)]()
+    return c
+
+
+@pytest.mark.parametrize("gates", [0, 1, 2, 3, 5])
+def test_pulled_run_gate_counts(qsim, oracle, gpu_ready, monkeypatch, gates):
+    """The edges of the pulled schedule (noise.hip launch_pull_noise_run) at the smallest size it
+    takes, 9 qubits: no gate (no pass), one (only the first set of words), two (both sets, no
+    reuse), three and five (a set reused once and twice); run twice on one object, so the second
+    run starts behind the first one's passes and on both code sets.  Maps on the side stream and
+    on the state's own give the same bits, and the oracle's state."""
+    monkeypatch.setenv("QSIM_NOISE_MAP_FUSED", "0")
+    monkeypatch.setenv("QSIM_NOISY_TILE", "0")
+    n, seed = 9, 31
+    c = _short_circuit(qsim, n, gates)
+    assert len(c.getGates()) == gates
+    channels = [(0, 0, 0.3), (3, n - 1, 0.2), (5, 4, 0.25), (4, 8, 0.4)]
+    want, ctr = oracle.noisy_run(n, oracle.gates_of(c), channels, seed)
+    want, _ = oracle.noisy_run(n, oracle.gates_of(c), channels, seed, ctr, want)
+    got = []
+    for overlap in ("1", "0"):
+        monkeypatch.setenv("QSIM_NOISE_MAP_OVERLAP", overlap)
+        sim = qsim.NoisySimulator(n, _model(qsim, channels))
+        sim.setSeed(seed)
+        sim.run(c)
+        sim.run(c)
+        got.append(sim.getStateVector())
+    assert np.array_equal(got[0], got[1])
+    np.testing.assert_allclose(got[0], want, atol=1e-12, rtol=0)
+
+
 def _read_device(ptr, n):
     """The 2^n complex amplitudes at a raw device pointer (hipMemcpy D2H via the loaded runtime)."""
     import ctypes

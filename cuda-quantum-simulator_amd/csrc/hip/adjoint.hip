@@ -226,8 +226,8 @@ PairGeom pair_geom(int n, const Generator& g) {
 }  // namespace
 
 void launch_pauli_apply(const double2* src, double2* dst, int n, const ExpectPlan& plan, DevBuf& terms,
-                        hipStream_t s, Timer* tm) {
-    const uint64_t N = 1ull << n;
+                        hipStream_t s, Timer* tm, uint64_t batch) {
+    const uint64_t N = batch << n;
     if (plan.terms.empty()) {  // H = 0
         QSIM_HIPCHK(hipMemsetAsync(dst, 0, sizeof(double2) * N, s));
         return;
@@ -236,15 +236,18 @@ void launch_pauli_apply(const double2* src, double2* dst, int n, const ExpectPla
     const ExpectTerm* d_terms = (const ExpectTerm*)terms.ptr;
     bool first = true;
     for (const ExpectGroup& g : plan.groups) {
-        launch_pauli_apply_group(src, dst, n, g.x, d_terms + g.begin, g.end - g.begin, first, s, tm);
+        launch_pauli_apply_group(src, dst, n, g.x, d_terms + g.begin, g.end - g.begin, first, s, tm, batch);
         first = false;
     }
 }
 
 void launch_pauli_apply_group(const double2* src, double2* dst, int n, uint64_t x, const ExpectTerm* d_terms,
-                              size_t count, bool first, hipStream_t s, Timer* tm) {
-    const uint64_t N = 1ull << n;
-    if (x >= N) fail(QSIM_ERR_INVALID_ARGUMENT, "x mask of a Pauli group outside the state");
+                              size_t count, bool first, hipStream_t s, Timer* tm, uint64_t batch) {
+    // (the masks lie below 2^n: i ^ x never leaves a member, and a member's index bits above n
+    // meet no z bit — the launch over batch x 2^n amplitudes is the single state's, longer)
+    if (batch < 1 || (batch << n) >> n != batch) fail(QSIM_ERR_INVALID_ARGUMENT, "bad member count of a Pauli-sum apply");
+    if (x >> n) fail(QSIM_ERR_INVALID_ARGUMENT, "x mask of a Pauli group outside the state");
+    const uint64_t N = batch << n;
     const unsigned blocks = (unsigned)std::min<uint64_t>((N + 255) / 256, 1u << 16);
     for (size_t t0 = 0; t0 < count; t0 += kExpectTerms) {
         const int nterms = (int)std::min<size_t>(kExpectTerms, count - t0);

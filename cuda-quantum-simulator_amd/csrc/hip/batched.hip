@@ -261,6 +261,9 @@ struct qsim_batch {
     // coefficient table of the last parameter sweep (qsim_batch_run_sweep): [slot][member][8]
     // doubles, grown on demand like d_frames
     DevBuf sweep_table;
+    // adjoint gradients of a sweep (qsim_batch_gradient_sweep): the two work ensembles and the
+    // plans of the inverted segments (null until used; qsim_batch_gradient_release drops them)
+    std::unique_ptr<BatchGradWork> grad;
     PlanCache plans;
     Timer timer;
     Scratch scratch, scratch2;
@@ -306,6 +309,7 @@ struct qsim_batch {
     SplitPart split[3];
     ~qsim_batch() {
         if (stream) (void)hipStreamSynchronize(stream);
+        grad.reset();
         noise.destroy();
         if (d0) (void)hipFree(d0);
         if (d1) (void)hipFree(d1);
@@ -729,6 +733,120 @@ int qsim_batch_sweep_plan(int n_qubits, int batch, const qsim_gate* gates, size_
         const Plan plan = plan_fused(sweep_lower(n_qubits, pg, {}, true), n_qubits);
         info[1] = (int32_t)plan.passes.size();
         for (size_t p = 0; p < plan.passes.size(); ++p) info[2] += pass_has_step_op(plan, p) ? 1 : 0;
+    });
+}
+
+// ---- adjoint gradients of a sweep (the kernels and the backward walk: batch_adjoint.hip) ----
+int qsim_batch_gradient_sweep(qsim_batch* b, const qsim_gate* gates, size_t count, const double* angles,
+                              size_t n_slots, const qsim_pauli_term* terms, size_t nterms, int flags, double* values,
+                              double* grads) {
+    bool backward = false;  // there is something to differentiate: P > 0 and H != 0
+    int rc = guarded([&] {
+        need(b);
+        std::vector<size_t> slots;
+        sweep_arguments(b->n, gates, count, flags, slots);
+        const size_t P = slots.size();
+        if (n_slots != P) fail(QSIM_ERR_INVALID_ARGUMENT, "n_slots must be the number of parameterised gates");
+        if (P && !angles) fail(QSIM_ERR_INVALID_ARGUMENT, "null angles");
+        if (!terms && nterms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        check_pauli_masks(b->n, terms, nterms, "Pauli term");
+        if (!values || (P && !grads)) fail(QSIM_ERR_INVALID_ARGUMENT, "null output");
+        backward = P > 0 && !lower_expectation(b->n, terms, nterms, nullptr).terms.empty();
+        // (the work ensembles before the forward run: a failed allocation leaves the members as they were)
+        if (backward) batch_grad_ensure(b->grad, b->n, (uint64_t)b->batch, P, b->stream);
+    });
+    if (rc != QSIM_OK) return rc;
+    // The forward run is the sweep itself (its angle checks come before its first launch): the
+    // members end exactly as it leaves them, and nothing below writes to them.
+    if (count > 0 && (rc = qsim_batch_run_sweep(b, gates, count, angles, n_slots, flags)) != QSIM_OK) return rc;
+    return guarded([&] {
+        const int n = b->n;
+        const size_t B = (size_t)b->batch, P = n_slots;
+        std::fill(values, values + B, 0.0);
+        if (P) std::fill(grads, grads + B * P, 0.0);
+        const int* perm = b->perm.empty() ? nullptr : b->perm.data();
+        // the values: what qsim_batch_expectation computes, the same way
+        const ExpectPlan eplan = lower_expectation(n, terms, nterms, perm);
+        if (eplan.terms.empty()) {  // H = 0 (no terms, or every coefficient cancels)
+            QSIM_HIPCHK(hipStreamSynchronize(b->stream));
+            return;
+        }
+        materialize(b);
+        double* d_val = (double*)b->scratch.get((B + B * expect_chunks(B)) * sizeof(double), b->stream);
+        launch_expectation(b->d, n, B, eplan, b->expect_terms, d_val + B, d_val, b->stream, &b->timer);
+        QSIM_HIPCHK(hipMemcpyAsync(values, d_val, B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        if (!backward) {
+            QSIM_HIPCHK(hipStreamSynchronize(b->stream));
+            return;
+        }
+        // phi = a copy of the ensemble where it lies, lambda = H phi under that layout
+        BatchGradWork& w = *b->grad;
+        QSIM_HIPCHK(hipMemcpyAsync(w.phi, b->d, (B * sizeof(double2)) << n, hipMemcpyDeviceToDevice, b->stream));
+        launch_pauli_apply(b->d, w.lam, n, lower_pauli_apply(n, terms, nterms, perm), w.terms, b->stream, &b->timer, B);
+        QSIM_HIPCHK(hipMemsetAsync(w.d_out, 0, P * B * sizeof(double), b->stream));
+        // the walk: the sweep's own placeholder ops at the slots, the other gates inverted, all under b->perm
+        std::vector<size_t> slots;
+        const std::vector<qsim_gate> pg = sweep_arguments(n, gates, count, flags, slots);
+        const std::vector<Op> ops = sweep_lower(n, pg, b->perm, true);
+        std::vector<BatchBackStep> steps;
+        for (size_t k = count; k-- > slots[0];) {  // (gates before the first parameter are never undone)
+            BatchBackStep st;
+            if (ops[k].src >= 0) {
+                st.op = ops[k];
+                st.pauli = gate_generator(gates[k]).pauli;
+            } else {
+                const qsim_gate inv = gate_inverse(gates[k]);
+                st.op = lower_gates(n, &inv, 1, b->perm)[0];
+                st.op.src = -1;
+            }
+            steps.push_back(st);
+        }
+        batch_adjoint_sweep(w, n, B, steps, (const double*)b->sweep_table.ptr, sweep_fused_path(n, flags), b->stream,
+                            &b->timer);
+        std::vector<double> by_slot(P * B);  // [slot][member] on the device, member-major for the caller
+        QSIM_HIPCHK(hipMemcpyAsync(by_slot.data(), w.d_out, P * B * sizeof(double), hipMemcpyDeviceToHost, b->stream));
+        QSIM_HIPCHK(hipStreamSynchronize(b->stream));
+        for (size_t t = 0; t < B; ++t)
+            for (size_t j = 0; j < P; ++j) grads[t * P + j] = by_slot[j * B + t];
+    });
+}
+
+int qsim_batch_gradient_release(qsim_batch* b) {
+    return guarded([&] {
+        need(b);
+        if (!b->grad) return;
+        QSIM_HIPCHK(hipStreamSynchronize(b->stream));
+        b->grad.reset();
+    });
+}
+
+int qsim_batch_gradient_plan(int n_qubits, int batch, const qsim_gate* gates, size_t count,
+                             const qsim_pauli_term* terms, size_t nterms, int flags, int32_t info[8]) {
+    return guarded([&] {
+        if (!info) fail(QSIM_ERR_INVALID_ARGUMENT, "null info");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > QSIM_MAX_QUBITS_SINGLE)
+            fail(QSIM_ERR_INVALID_ARGUMENT, "Number of qubits must be between 1 and 30");
+        if (batch < 1) fail(QSIM_ERR_INVALID_ARGUMENT, "batch_size must be positive");
+        std::vector<size_t> slots;
+        sweep_arguments(n_qubits, gates, count, flags, slots);
+        if (!terms && nterms) fail(QSIM_ERR_INVALID_ARGUMENT, "null term list");
+        check_pauli_masks(n_qubits, terms, nterms, "Pauli term");
+        for (int i = 0; i < 8; ++i) info[i] = 0;
+        info[0] = (int32_t)slots.size();
+        bool in_segment = false;
+        for (size_t k = slots.empty() ? count : slots[0]; k < count; ++k) {
+            if (gate_is_parameterised(gates[k].type)) {
+                in_segment = false;
+            } else if (!in_segment) {  // (gates before the first parameter are never undone)
+                ++info[1];
+                in_segment = true;
+            }
+        }
+        info[2] = (int32_t)lower_pauli_apply(n_qubits, terms, nterms, nullptr).launches;
+        info[3] = sweep_fused_path(n_qubits, flags) ? 1 : 0;
+        const uint64_t bytes = (2ull * (uint64_t)batch * sizeof(double2)) << n_qubits;
+        info[4] = (int32_t)(uint32_t)(bytes & 0xffffffffull);
+        info[5] = (int32_t)(uint32_t)(bytes >> 32);
     });
 }
 

@@ -854,9 +854,10 @@ void check_gradient_args(int n, const qsim_gate* gates, size_t count, const qsim
 // (cr, ci) is its complex weight c (-i)^nY (the kernel adds the sign (-1)^popcount(i & z)).
 ExpectPlan lower_pauli_apply(int n, const qsim_pauli_term* terms, size_t count, const int* perm);
 // dst = H src out of place (src != dst), one streaming pass per launch of the plan; an empty plan
-// zeroes dst.  terms: the owner's device copy of the term table.  Asynchronous.
+// zeroes dst.  terms: the owner's device copy of the term table.  batch: src and dst hold that many
+// members of 2^n amplitudes, each multiplied by H on its own.  Asynchronous.
 void launch_pauli_apply(const double2* src, double2* dst, int n, const ExpectPlan& plan, DevBuf& terms,
-                        hipStream_t s, Timer* tm);
+                        hipStream_t s, Timer* tm, uint64_t batch = 1);
 // *d_re + i *d_im = <a| G |b> (either may be null), d_partials: 2 * expect_chunks(1) doubles.
 void launch_braket(const double2* a, const double2* b, int n, const Generator& g, double* d_partials, double* d_re,
                    double* d_im, hipStream_t s, Timer* tm);
@@ -868,7 +869,7 @@ void launch_adjoint_step(double2* phi, double2* lam, int n, const Generator& g, 
 // One launch of it per kExpectTerms terms of one group: dst[i] (+)= W(i) src[i ^ x] over the
 // `count` device terms at d_terms; first: the first launch writes dst, later ones accumulate.
 void launch_pauli_apply_group(const double2* src, double2* dst, int n, uint64_t x, const ExpectTerm* d_terms,
-                              size_t count, bool first, hipStream_t s, Timer* tm);
+                              size_t count, bool first, hipStream_t s, Timer* tm, uint64_t batch = 1);
 
 // Pauli-string rotations exp(-i theta/2 P) (pauli_rot.hip).  A rotation under the state's layout:
 // physical masks (the convention of qsim_pauli_term) and the angle.
@@ -1022,6 +1023,52 @@ struct Scratch {
     void* get(size_t bytes, hipStream_t s);
     ~Scratch();
 };
+
+// Adjoint gradients of a batched parameter sweep (batch_adjoint.hip; the entry points and what they
+// share with the sweep: batched.hip).  The work of the backward sweep: two ensembles ([batch][2^n]
+// each) kept across calls, one result per (slot, member), the per-work-group partial sums of a step
+// and, on the cross-check path (QSIM_ADJOINT_FUSED=0) alone, one slot's conjugated coefficients.
+struct BatchGradWork {
+    double2* phi = nullptr;
+    double2* lam = nullptr;
+    double* d_out = nullptr;  // out_cap doubles: [slot][member]
+    size_t out_cap = 0;
+    double* d_partials = nullptr;  // batch_adjoint_partials doubles
+    double* d_conj = nullptr;      // [batch][8]
+    DevBuf ops, stages, terms;
+    PlanCache plans;  // the inverted fixed segments
+    BatchGradWork() = default;
+    BatchGradWork(const BatchGradWork&) = delete;
+    BatchGradWork& operator=(const BatchGradWork&) = delete;
+    ~BatchGradWork();
+};
+// The work for `batch` members of n qubits and n_slots parameters, allocated on first use (d_out
+// grows on demand; s: the stream its users run on).  A refused allocation clears the HIP error,
+// drops the whole work (slot becomes null) and throws Error (QSIM_ERR_DEVICE).
+BatchGradWork& batch_grad_ensure(std::unique_ptr<BatchGradWork>& slot, int n, uint64_t batch, size_t n_slots,
+                                 hipStream_t s);
+size_t batch_adjoint_partials(int n, uint64_t batch);  // doubles of d_partials a step may write
+// d_out[t] = Im <lam_t| G |phi_t> for every member t < batch, then (apply) member t's U^† on both
+// of its work states, in one launch; without apply nothing is stored (the bra-ket alone, coef may
+// be null).  kind: how the rotation lowers (K_M1 with g.pauli 1 / 2, K_DIAG with 3); g: physical
+// positions; coef: the FORWARD coefficients, [batch][8] in Op::m layout.  Asynchronous.
+void launch_batch_adjoint_step(double2* phi, double2* lam, int n, uint64_t batch, const Generator& g, int kind,
+                               const double* coef, bool apply, double* d_partials, double* d_out, hipStream_t s,
+                               Timer* tm);
+// One step of the backward walk (execution order: the circuit's last gate first).  pauli == 0: a
+// non-parameterised gate, op = its lowered inverse; else a parameterised gate generating that
+// Pauli, op = the sweep's placeholder op (kind, target, control; src = its slot).
+struct BatchBackStep {
+    Op op;
+    int pauli = 0;
+};
+// The backward sweep over w.phi / w.lam (already holding phi and H phi): w.d_out[slot * batch + t]
+// for every slot among `steps`, whose last entry is the first parameterised gate (bra-ket only).
+// d_tab: the sweep's table, [slot][member][8].  fused_segments: runs of non-parameterised steps go
+// through launch_fused and w.plans (a plan with a relayout pass is an error), else launch_op.
+// QSIM_ADJOINT_FUSED=0 composes each step from the bra-ket and two launch_sweep_op calls.
+void batch_adjoint_sweep(BatchGradWork& w, int n, uint64_t batch, const std::vector<BatchBackStep>& steps,
+                         const double* d_tab, bool fused_segments, hipStream_t s, Timer* tm);
 
 // RAII scope used around each launch.  Record mode: events recorded on the stream before and
 // after the launch (two marker packets, ~8 us of serialisation per launch — 35 % of a 20-qubit

@@ -8,6 +8,7 @@
 #include <stdexcept>
 
 #include "abi_util.hpp"
+#include "qsim/Observable.hpp"
 
 namespace qsim {
 
@@ -164,22 +165,51 @@ void BatchedSimulator::run(const Circuit& circuit) {
                              (noise_ == BatchedNoise::Reference ? QSIM_BATCH_REFERENCE_NOISE : 0)));
 }
 
-void BatchedSimulator::runSweep(const Circuit& circuit, const std::vector<double>& angles) {
-    if (circuit.getNumQubits() != num_qubits_)
+// The checks of a sweep made on this side of the ABI; returns the number of slots.
+static size_t sweep_slots(const Circuit& circuit, const std::vector<qsim_gate>& gates, size_t n_angles, int num_qubits,
+                          int batch_size, bool noise_free, bool full_physical) {
+    if (circuit.getNumQubits() != num_qubits)
         throw std::invalid_argument("Circuit qubit count doesn't match simulator");
-    if (!noise_model_.getChannels().empty())
-        throw std::invalid_argument("runSweep is noise-free: the noise model must be empty");
-    if (gate_set_ != BatchedGateSet::Full || noise_ != BatchedNoise::Physical)
+    if (!noise_free) throw std::invalid_argument("runSweep is noise-free: the noise model must be empty");
+    if (!full_physical)
         throw std::invalid_argument("runSweep needs the full gate set and the physical noise semantics");
-    const std::vector<qsim_gate> gates = detail::toAbi(circuit);
     size_t slots = 0;
     for (const qsim_gate& g : gates)
         slots += g.type == QSIM_GATE_RX || g.type == QSIM_GATE_RY || g.type == QSIM_GATE_RZ ||
                  g.type == QSIM_GATE_CRY || g.type == QSIM_GATE_CRZ;
-    if (angles.size() != slots * (size_t)batch_size_)
+    if (n_angles != slots * (size_t)batch_size)
         throw std::invalid_argument("angles must hold batch_size x (parameterised gates) values");
+    return slots;
+}
+
+void BatchedSimulator::runSweep(const Circuit& circuit, const std::vector<double>& angles) {
+    const std::vector<qsim_gate> gates = detail::toAbi(circuit);
+    const size_t slots = sweep_slots(circuit, gates, angles.size(), num_qubits_, batch_size_,
+                                     noise_model_.getChannels().empty(),
+                                     gate_set_ == BatchedGateSet::Full && noise_ == BatchedNoise::Physical);
     check(qsim_batch_run_sweep(h_, gates.data(), gates.size(), angles.data(), slots, 0));
 }
+
+BatchedSimulator::SweepGradient BatchedSimulator::gradientSweep(const Circuit& circuit,
+                                                                const std::vector<double>& angles,
+                                                                const PauliSum& observable) {
+    const std::vector<qsim_gate> gates = detail::toAbi(circuit);
+    const size_t slots = sweep_slots(circuit, gates, angles.size(), num_qubits_, batch_size_,
+                                     noise_model_.getChannels().empty(),
+                                     gate_set_ == BatchedGateSet::Full && noise_ == BatchedNoise::Physical);
+    if (observable.getNumQubits() != num_qubits_)
+        throw std::invalid_argument("Observable qubit count doesn't match simulator");
+    std::vector<qsim_pauli_term> terms;
+    terms.reserve(observable.size());
+    for (const PauliSum::Term& t : observable.terms()) terms.push_back(qsim_pauli_term{t.x_mask, t.z_mask, t.coeff});
+    SweepGradient g{std::vector<double>((size_t)batch_size_, 0.0),
+                    std::vector<double>((size_t)batch_size_ * slots, 0.0)};
+    check(qsim_batch_gradient_sweep(h_, gates.data(), gates.size(), angles.data(), slots, terms.data(), terms.size(), 0,
+                                    g.values.data(), g.gradients.data()));
+    return g;
+}
+
+void BatchedSimulator::releaseGradientBuffers() { check(qsim_batch_gradient_release(h_)); }
 
 std::vector<double> BatchedSimulator::getAverageProbabilities() const {
     std::vector<double> p(size_t(1) << num_qubits_);

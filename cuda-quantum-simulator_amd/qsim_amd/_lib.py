@@ -174,6 +174,11 @@ _sig(hip, "qsim_batch_run", [_P, POINTER(qsim_gate), c_size_t, POINTER(qsim_nois
                              c_size_t, c_int])
 _sig(hip, "qsim_batch_run_sweep", [_P, POINTER(qsim_gate), c_size_t, POINTER(c_double), c_size_t, c_int])
 _sig(hip, "qsim_batch_sweep_plan", [c_int, c_int, POINTER(qsim_gate), c_size_t, c_int, POINTER(c_int32)])
+_sig(hip, "qsim_batch_gradient_sweep", [_P, POINTER(qsim_gate), c_size_t, POINTER(c_double), c_size_t,
+                                        POINTER(qsim_pauli_term), c_size_t, c_int, POINTER(c_double), POINTER(c_double)])
+_sig(hip, "qsim_batch_gradient_release", [_P])
+_sig(hip, "qsim_batch_gradient_plan", [c_int, c_int, POINTER(qsim_gate), c_size_t, POINTER(qsim_pauli_term), c_size_t,
+                                       c_int, POINTER(c_int32)])
 _sig(hip, "qsim_batch_avg_probabilities", [_P, _P])
 _sig(hip, "qsim_batch_traj_probabilities", [_P, c_int, _P])
 _sig(hip, "qsim_batch_traj_state", [_P, c_int, _P])

@@ -293,6 +293,22 @@ def batch_sweep_plan(circuit: Circuit, batch_size: int, per_gate: bool = False) 
             "table_bytes": (info[4] & 0xffffffff) | ((info[5] & 0xffffffff) << 32), "fused": bool(info[6])}
 
 
+def batch_gradient_plan(circuit: Circuit, batch_size: int, observable, per_gate: bool = False) -> dict:
+    """What BatchedSimulator.gradientSweep would do for this circuit and observable on batch_size
+    members (qsim_batch_gradient_plan, host only): slots, segments (inverted runs of non-parameterised
+    gates the backward sweep applies; gates before the first parameter are never undone),
+    apply_launches (of lambda = H phi), fused (False: the segments run gate by gate) and work_bytes
+    (the two work ensembles: 2 x batch_size x 2^n x 16)."""
+    n = circuit.getNumQubits()
+    arr, cnt = circuit.to_abi()
+    terms, nterms = observable.to_abi(n)
+    info = (ctypes.c_int32 * 8)()
+    flags = _lib.QSIM_BATCH_PER_GATE if per_gate else 0
+    _lib.check(_lib.hip.qsim_batch_gradient_plan(n, int(batch_size), arr, cnt, terms, nterms, flags, info))
+    return {"slots": info[0], "segments": info[1], "apply_launches": info[2], "fused": bool(info[3]),
+            "work_bytes": (info[4] & 0xffffffff) | ((info[5] & 0xffffffff) << 32)}
+
+
 def _perm_arg(n: int, perm):
     if perm is None:
         return None

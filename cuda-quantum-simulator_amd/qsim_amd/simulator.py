@@ -717,23 +717,51 @@ class BatchedSimulator:
         Noise-free, from whatever every member holds; one planned run whatever the angles.
         ValueError: a shape mismatch, a non-empty noise model, the reference gate set or the
         reference noise semantics selected (construct with noise=BatchedNoise.Physical)."""
+        a, n_slots = self._sweep_angles(circuit, angles)
+        g, ng = circuit.to_abi()
+        flags = _lib.QSIM_BATCH_PER_GATE if per_gate else 0
+        _lib.check(_lib.hip.qsim_batch_run_sweep(self._h, g, ng, a.ctypes.data_as(_c.POINTER(_c.c_double)),
+                                                 n_slots, flags))
+
+    def _sweep_angles(self, circuit: Circuit, angles):
+        """The checks of a sweep made on this side of the ABI; returns the contiguous (B, P) angles
+        and P."""
         if circuit.getNumQubits() != self._n:
             raise ValueError("Circuit qubit count doesn't match simulator")
         if self._noise.to_abi()[1] > 0:
             raise ValueError("runSweep is noise-free: the noise model must be empty")
         if self._gate_set != BatchedGateSet.Full or self._noise_sem != BatchedNoise.Physical:
             raise ValueError("runSweep needs the full gate set and the physical noise semantics")
-        g, ng = circuit.to_abi()
         n_slots = sum(1 for op in circuit.getGates() if op.type in PARAMETRIC)
         a = np.asarray(angles, dtype=np.float64)
         if a.ndim == 1:
             a = np.broadcast_to(a, (self._b, a.shape[0]))
         if a.ndim != 2 or a.shape != (self._b, n_slots):
             raise ValueError(f"angles must have shape ({self._b}, {n_slots}) or ({n_slots},)")
-        a = np.ascontiguousarray(a)
+        return np.ascontiguousarray(a), n_slots
+
+    def gradientSweep(self, circuit: Circuit, angles, observable, per_gate: bool = False):
+        """runSweep(circuit, angles, per_gate), then every member's energy and its gradient by the
+        adjoint method (qsim_batch_gradient_sweep; no reference counterpart): returns (values[B],
+        grads[B, P]), grads[t, k] = d values[t] / d angles[t, k] — indexed by slot like angles, not
+        by gate as Simulator.gradient.  One forward run and one backward sweep over two work
+        ensembles of the batch's size, which stay on the object until releaseGradientBuffers().
+        The members are left exactly as runSweep leaves them; values are what getExpectations then
+        returns.  angles and the ValueErrors are those of runSweep."""
+        a, n_slots = self._sweep_angles(circuit, angles)
+        g, ng = circuit.to_abi()
+        terms, nterms = observable.to_abi(self._n)
+        values = np.zeros(self._b, dtype=np.float64)
+        grads = np.zeros((self._b, n_slots), dtype=np.float64)
+        dp = _c.POINTER(_c.c_double)
         flags = _lib.QSIM_BATCH_PER_GATE if per_gate else 0
-        _lib.check(_lib.hip.qsim_batch_run_sweep(self._h, g, ng, a.ctypes.data_as(_c.POINTER(_c.c_double)),
-                                                 n_slots, flags))
+        _lib.check(_lib.hip.qsim_batch_gradient_sweep(self._h, g, ng, a.ctypes.data_as(dp), n_slots, terms, nterms,
+                                                      flags, values.ctypes.data_as(dp), grads.ctypes.data_as(dp)))
+        return values, grads
+
+    def releaseGradientBuffers(self) -> None:
+        """Free the work ensembles of gradientSweep (the next call allocates them again)."""
+        _lib.check(_lib.hip.qsim_batch_gradient_release(self._h))
 
     def synchronize(self) -> None: _lib.check(_lib.hip.qsim_batch_sync(self._h))
 

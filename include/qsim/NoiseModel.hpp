@@ -142,6 +142,19 @@ public:
     // the reference gate set or the reference noise semantics is configured (a sweep needs
     // setNoiseSemantics(BatchedNoise::Physical) and an empty noise model).
     void runSweep(const Circuit& circuit, const std::vector<double>& angles);
+    // Adjoint-method gradients of a sweep (no reference counterpart; qsim_batch_gradient_sweep):
+    // runSweep(circuit, angles), then values[t] = <psi_t|H|psi_t> and gradients[t * P + k] =
+    // d values[t] / d angles[t * P + k], from one backward sweep over two work ensembles of the
+    // batch's size, which stay on the object until releaseGradientBuffers().  The trajectories are
+    // left exactly as runSweep leaves them.  The exceptions of runSweep; std::invalid_argument
+    // also on an observable of another qubit count.
+    struct SweepGradient {
+        std::vector<double> values;     // B
+        std::vector<double> gradients;  // B x P, trajectory-major
+    };
+    SweepGradient gradientSweep(const Circuit& circuit, const std::vector<double>& angles,
+                                const PauliSum& observable);
+    void releaseGradientBuffers();
 
     std::vector<double> getAverageProbabilities() const;
     std::vector<double> getProbabilities(int trajectory_idx) const;  // std::out_of_range

@@ -541,6 +541,38 @@ int qsim_batch_run_sweep(qsim_batch* b, const qsim_gate* gates, size_t count,
  * [7] = 0.  The argument errors of the run. */
 int qsim_batch_sweep_plan(int n_qubits, int batch, const qsim_gate* gates, size_t count, int flags,
                           int32_t info[8]);
+/* Adjoint-method gradients of a sweep (no reference counterpart): the sweep above, then member t's
+ * energy values[t] = <psi_t|H|psi_t> and grads[t * n_slots + j] = dE_t / d angles[t * n_slots + j],
+ * indexed by slot like `angles` (not by gate as qsim_state_gradient), from one forward run and one
+ * backward sweep over two work ensembles.
+ * Arguments are checked as qsim_batch_run_sweep (gates, flags, angles, n_slots) and
+ * qsim_state_gradient (terms) check them, with their error codes, before the first launch; null
+ * values, or null grads with P > 0: QSIM_ERR_INVALID_ARGUMENT.
+ * The forward run is qsim_batch_run_sweep itself: afterwards the members and qsim_batch_perm are
+ * bitwise what it leaves, and the backward sweep does not write to them.  values are what
+ * qsim_batch_expectation returns for that state, bitwise.
+ * The backward sweep works on phi (a device copy of the ensemble where it lies) and lambda = H phi,
+ * B * 2^n amplitudes each, kept on the object across calls until qsim_batch_gradient_release or
+ * destroy; they are allocated before the forward run, and a failed allocation returns
+ * QSIM_ERR_DEVICE with the members untouched.  Per member the recurrence is qsim_state_gradient's;
+ * at a parameterised gate one launch covers all members (the bra-ket and U^† on both work states,
+ * member t's U^† derived from the sweep's coefficient table), non-parameterised segments between
+ * them are inverted and run as fused tile passes (n >= 10, no QSIM_BATCH_PER_GATE) or per gate.
+ * QSIM_ADJOINT_FUSED=0 composes each step from a bra-ket and two per-gate launches (cross-check).
+ * P == 0 or H == 0 (no terms, or all cancel): values only (zeros for H == 0), grads zero-filled.
+ * count == 0: the values of the current states.  Synchronous; bitwise reproducible; member t's
+ * outputs do not depend on the other members' angles. */
+int qsim_batch_gradient_sweep(qsim_batch* b, const qsim_gate* gates, size_t count, const double* angles,
+                              size_t n_slots, const qsim_pauli_term* terms, size_t nterms, int flags,
+                              double* values /* B */, double* grads /* B * n_slots, row-major by member */);
+/* Frees the work ensembles of qsim_batch_gradient_sweep (the next call allocates them again). */
+int qsim_batch_gradient_release(qsim_batch* b);
+/* Host-only (no GPU): what the call above would do.  info[0] = P; [1] = inverted non-parameterised
+ * segments the backward sweep runs (gates before the first parameter are never undone); [2] =
+ * launches of lambda = H phi; [3] = 1 if the fused path is taken; [4], [5] = work bytes
+ * (2 * batch * 2^n * 16), low and high word; [6] = [7] = 0.  The argument errors of the call. */
+int qsim_batch_gradient_plan(int n_qubits, int batch, const qsim_gate* gates, size_t count,
+                             const qsim_pauli_term* terms, size_t nterms, int flags, int32_t info[8]);
 int qsim_batch_avg_probabilities(qsim_batch* b, double* dst);           /* 2^n */
 int qsim_batch_traj_probabilities(qsim_batch* b, int traj, double* dst);  /* 2^n */
 int qsim_batch_traj_state(qsim_batch* b, int traj, double* dst);          /* 2*2^n */

@@ -1073,6 +1073,110 @@ int qsim_batch_expectation(qsim_batch* b, const qsim_pauli_term* terms, size_t c
     });
 }
 
+// ---- overlap matrices (the kernels: batch_overlap.hip) ----
+static bool overlap_mfma_enabled() { return env_switch("QSIM_OVERLAP_MFMA", true); }
+static bool same_layout(const std::vector<int>& p, const std::vector<int>& q) {
+    const size_t n = std::max(p.size(), q.size());
+    for (size_t i = 0; i < n; ++i)
+        if ((p.empty() ? (int)i : p[i]) != (q.empty() ? (int)i : q[i])) return false;
+    return true;
+}
+// The partial tiles and the Ba x Bb result in a's scratch, before anything is launched: a refused
+// allocation is QSIM_ERR_DEVICE with the HIP error cleared and every amplitude where it was.
+static double2* overlap_scratch(qsim_batch* a, const OverlapPlan& p, uint64_t entries) {
+    const size_t bytes = p.scratch_bytes + entries * sizeof(double2);
+    Scratch& sc = a->scratch;
+    if (bytes > sc.cap) {
+        if (sc.ptr) {
+            QSIM_HIPCHK(hipStreamSynchronize(a->stream));
+            QSIM_HIPCHK(hipFree(sc.ptr));
+            sc.ptr = nullptr;
+            sc.cap = 0;
+        }
+        if (!(sc.ptr = device_alloc_or_null(bytes))) fail(QSIM_ERR_DEVICE, "no device memory for the overlap scratch");
+        sc.cap = bytes;
+    }
+    return (double2*)sc.ptr;
+}
+// out = the Ba x Bb overlaps of a's members with the Bb vectors at d_b (null: a's own, the self
+// case), both already in one layout and complete on their streams.
+static void overlap_into(qsim_batch* a, const double2* d_b, uint64_t Bb, const OverlapPlan& p, double2* d_work, double* out) {
+    const uint64_t Ba = (uint64_t)a->batch;
+    const bool self = d_b == nullptr;
+    double2* d_out = d_work + p.scratch_bytes / sizeof(double2);
+    launch_batch_overlap(a->d, self ? a->d : d_b, a->n, Ba, Bb, self, p, d_work, d_out, a->stream, &a->timer);
+    QSIM_HIPCHK(hipMemcpyAsync(out, d_out, Ba * Bb * sizeof(double2), hipMemcpyDeviceToHost, a->stream));
+    QSIM_HIPCHK(hipStreamSynchronize(a->stream));
+}
+
+// Self: reads a->d under a->perm like qsim_batch_expectation (G does not depend on a relabeling all
+// members share).  Cross: in place when the two layouts agree, else both are restored.
+int qsim_batch_overlaps(qsim_batch* a, qsim_batch* b, double* out) {
+    return guarded([&] {
+        need(a);
+        if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
+        const bool self = !b || b == a;
+        if (!self && a->n != b->n) fail(QSIM_ERR_INVALID_ARGUMENT, "ensembles have different qubit counts");
+        if (!self && a->device != b->device) fail(QSIM_ERR_INVALID_ARGUMENT, "ensembles live on different devices");
+        const uint64_t Ba = (uint64_t)a->batch, Bb = self ? Ba : (uint64_t)b->batch;
+        const OverlapPlan p = overlap_plan(a->n, Ba, Bb, self, overlap_mfma_enabled());
+        double2* d_work = overlap_scratch(a, p, Ba * Bb);
+        if (self) {
+            materialize(a);
+        } else if (same_layout(a->perm, b->perm)) {
+            materialize(a);
+            materialize(b);
+        } else {  // one common layout: the identity
+            canonicalize(a);
+            canonicalize(b);
+        }
+        if (!self) QSIM_HIPCHK(hipStreamSynchronize(b->stream));  // b's writes done; a's stream orders the rest
+        overlap_into(a, self ? nullptr : b->d, Bb, p, d_work, out);
+    });
+}
+
+int qsim_batch_state_overlaps(qsim_batch* a, qsim_state* s, double* out) {
+    return guarded([&] {
+        need(a);
+        check_state(s);
+        if (!out) fail(QSIM_ERR_INVALID_ARGUMENT, "null out");
+        if (a->n != s->n) fail(QSIM_ERR_INVALID_ARGUMENT, "ensemble and state have different qubit counts");
+        if (a->device != s->device) fail(QSIM_ERR_INVALID_ARGUMENT, "ensemble and state live on different devices");
+        const OverlapPlan p = overlap_plan(a->n, (uint64_t)a->batch, 1, false, false);
+        double2* d_work = overlap_scratch(a, p, (uint64_t)a->batch);
+        share_flush(s);
+        if (same_layout(a->perm, s->perm)) {
+            materialize(a);
+        } else {
+            canonicalize(a);
+            prep(s, false);
+        }
+        QSIM_HIPCHK(hipStreamSynchronize(s->stream));
+        overlap_into(a, s->d, 1, p, d_work, out);
+    });
+}
+
+int qsim_batch_overlap_plan(int n_qubits, int batch_a, int batch_b, int self, int32_t info[8]) {
+    return guarded([&] {
+        if (!info) fail(QSIM_ERR_INVALID_ARGUMENT, "null info");
+        if (n_qubits < QSIM_MIN_QUBITS || n_qubits > QSIM_MAX_QUBITS_SINGLE)
+            fail(QSIM_ERR_INVALID_ARGUMENT, "Number of qubits must be between 1 and 30");
+        if (batch_a < 1 || batch_b < 1) fail(QSIM_ERR_INVALID_ARGUMENT, "batch_size must be positive");
+        if (self && batch_a != batch_b) fail(QSIM_ERR_INVALID_ARGUMENT, "the self case has one batch size");
+        const OverlapPlan p =
+            overlap_plan(n_qubits, (uint64_t)batch_a, (uint64_t)batch_b, self != 0, overlap_mfma_enabled());
+        if (p.tiles > 0x7fffffffull) fail(QSIM_ERR_INVALID_ARGUMENT, "too many members for one overlap launch");
+        info[0] = p.mfma ? 1 : 0;
+        info[1] = (int32_t)p.tiles_a;
+        info[2] = (int32_t)p.tiles_b;
+        info[3] = (int32_t)p.tiles;
+        info[4] = (int32_t)p.chunks;
+        info[5] = (int32_t)(uint32_t)(p.scratch_bytes & 0xffffffffull);
+        info[6] = (int32_t)(uint32_t)(p.scratch_bytes >> 32);
+        info[7] = 0;
+    });
+}
+
 int qsim_batch_device_ptr(qsim_batch* b, void** dptr) {
     return guarded([&] {
         need(b);

@@ -1070,6 +1070,24 @@ struct BatchBackStep {
 void batch_adjoint_sweep(BatchGradWork& w, int n, uint64_t batch, const std::vector<BatchBackStep>& steps,
                          const double* d_tab, bool fused_segments, hipStream_t s, Timer* tm);
 
+// Overlap matrices of batched ensembles (batch_overlap.hip; the entry points: batched.hip).  How
+// out[i][j] = <a_i|b_j> (Ba x Bb members of n qubits) is cut up: tiles of 64 x 64 members — self:
+// only those of the upper triangle — times chunks of K = 2^n, one work-group and one partial tile
+// of scratch each.  A function of the arguments alone.
+struct OverlapPlan {
+    bool mfma = false;  // the matrix-core tile kernel (never for Bb == 1), else the FMA one
+    uint64_t tiles_a = 0, tiles_b = 0, tiles = 0;
+    uint32_t chunks = 1;
+    uint64_t chunk_len = 0;      // k per chunk (K / chunks)
+    uint64_t scratch_bytes = 0;  // chunks x tiles x 64 x 64 x 16
+};
+OverlapPlan overlap_plan(int n, uint64_t Ba, uint64_t Bb, bool self, bool mfma);
+// d_out[i * Bb + j] = <a_i|b_j>, a: [Ba][2^n], b: [Bb][2^n] (self: b == a and Bb == Ba; the result
+// is Hermitian bitwise with +0 imaginary parts on the diagonal).  d_partials: p.scratch_bytes.  The
+// tile kernel and the reduction that adds the chunks of an entry in order.  Asynchronous.
+void launch_batch_overlap(const double2* a, const double2* b, int n, uint64_t Ba, uint64_t Bb, bool self,
+                          const OverlapPlan& p, double2* d_partials, double2* d_out, hipStream_t s, Timer* tm);
+
 // RAII scope used around each launch.  Record mode: events recorded on the stream before and
 // after the launch (two marker packets, ~8 us of serialisation per launch — 35 % of a 20-qubit
 // circuit).  Ext mode (ext = true): the two events are handed to the launch itself through

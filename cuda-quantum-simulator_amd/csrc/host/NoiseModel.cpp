@@ -211,6 +211,33 @@ BatchedSimulator::SweepGradient BatchedSimulator::gradientSweep(const Circuit& c
 
 void BatchedSimulator::releaseGradientBuffers() { check(qsim_batch_gradient_release(h_)); }
 
+static std::vector<std::complex<double>> overlaps_of(qsim_batch* a, qsim_batch* b, size_t rows, size_t cols) {
+    std::vector<std::complex<double>> g(rows * cols);
+    check(qsim_batch_overlaps(a, b, reinterpret_cast<double*>(g.data())));
+    return g;
+}
+static std::vector<double> squared_moduli(const std::vector<std::complex<double>>& g) {
+    std::vector<double> k(g.size());
+    for (size_t i = 0; i < g.size(); ++i) k[i] = g[i].real() * g[i].real() + g[i].imag() * g[i].imag();
+    return k;
+}
+
+std::vector<std::complex<double>> BatchedSimulator::overlapMatrix() {
+    return overlaps_of(h_, nullptr, (size_t)batch_size_, (size_t)batch_size_);
+}
+std::vector<std::complex<double>> BatchedSimulator::overlapMatrix(BatchedSimulator& other) {
+    return overlaps_of(h_, other.h_, (size_t)batch_size_, (size_t)other.batch_size_);
+}
+std::vector<double> BatchedSimulator::kernelMatrix() { return squared_moduli(overlapMatrix()); }
+std::vector<double> BatchedSimulator::kernelMatrix(BatchedSimulator& other) {
+    return squared_moduli(overlapMatrix(other));
+}
+std::vector<std::complex<double>> BatchedSimulator::overlapsWith(StateVector& state) {
+    std::vector<std::complex<double>> v((size_t)batch_size_);
+    check(qsim_batch_state_overlaps(h_, state.handle(), reinterpret_cast<double*>(v.data())));
+    return v;
+}
+
 std::vector<double> BatchedSimulator::getAverageProbabilities() const {
     std::vector<double> p(size_t(1) << num_qubits_);
     check(qsim_batch_avg_probabilities(h_, p.data()));

@@ -179,6 +179,9 @@ _sig(hip, "qsim_batch_gradient_sweep", [_P, POINTER(qsim_gate), c_size_t, POINTE
 _sig(hip, "qsim_batch_gradient_release", [_P])
 _sig(hip, "qsim_batch_gradient_plan", [c_int, c_int, POINTER(qsim_gate), c_size_t, POINTER(qsim_pauli_term), c_size_t,
                                        c_int, POINTER(c_int32)])
+_sig(hip, "qsim_batch_overlaps", [_P, _P, POINTER(c_double)])
+_sig(hip, "qsim_batch_state_overlaps", [_P, _P, POINTER(c_double)])
+_sig(hip, "qsim_batch_overlap_plan", [c_int, c_int, c_int, c_int, POINTER(c_int32)])
 _sig(hip, "qsim_batch_avg_probabilities", [_P, _P])
 _sig(hip, "qsim_batch_traj_probabilities", [_P, c_int, _P])
 _sig(hip, "qsim_batch_traj_state", [_P, c_int, _P])

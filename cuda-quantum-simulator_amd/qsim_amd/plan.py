@@ -309,6 +309,21 @@ def batch_gradient_plan(circuit: Circuit, batch_size: int, observable, per_gate:
             "work_bytes": (info[4] & 0xffffffff) | ((info[5] & 0xffffffff) << 32)}
 
 
+def batch_overlap_plan(n: int, batch: int, other_batch=None) -> dict:
+    """How BatchedSimulator.overlapMatrix cuts its work up for `batch` members of n qubits against
+    other_batch members (None: the ensemble's own Gram matrix) (qsim_batch_overlap_plan, host
+    only): mfma (False: the FMA kernel — one column, or QSIM_OVERLAP_MFMA=0), row_tiles,
+    col_tiles, tiles (launched; the self case computes the upper triangle only), chunks (of
+    K = 2^n; one work-group per tile and chunk) and scratch_bytes (chunks x tiles x 64 x 64 x 16).
+    Everything but mfma depends on the arguments alone."""
+    self_case = other_batch is None
+    info = (ctypes.c_int32 * 8)()
+    _lib.check(_lib.hip.qsim_batch_overlap_plan(int(n), int(batch), int(batch if self_case else other_batch),
+                                                1 if self_case else 0, info))
+    return {"mfma": bool(info[0]), "row_tiles": info[1], "col_tiles": info[2], "tiles": info[3], "chunks": info[4],
+            "scratch_bytes": (info[5] & 0xffffffff) | ((info[6] & 0xffffffff) << 32)}
+
+
 def _perm_arg(n: int, perm):
     if perm is None:
         return None

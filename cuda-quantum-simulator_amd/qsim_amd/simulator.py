@@ -799,6 +799,46 @@ class BatchedSimulator:
                                                    out.ctypes.data_as(_c.POINTER(_c.c_double))))
         return out
 
+    def overlapMatrix(self, other: Optional["BatchedSimulator"] = None) -> np.ndarray:
+        """G[i, j] = <psi_i|phi_j> over this ensemble's members and other's, complex128 (B, B'),
+        computed where the members lie (qsim_batch_overlaps; no reference counterpart).  other
+        None (or self): the ensemble's own Gram matrix, Hermitian bitwise with +0 imaginary parts
+        on the diagonal, read under whatever layout the last run left (perm() and the amplitudes
+        stay as they are).  With another ensemble the two are read in place when their layouts
+        agree, else both layouts are restored first.  Bitwise reproducible; QSIM_OVERLAP_MFMA=0
+        selects the FMA kernel (cross-check).  ValueError: different qubit counts."""
+        cross = other is not None and other is not self
+        out = np.empty((self._b, other._b if cross else self._b), dtype=np.complex128)
+        _lib.check(_lib.hip.qsim_batch_overlaps(self._h, other._h if cross else None,
+                                                out.ctypes.data_as(_c.POINTER(_c.c_double))))
+        return out
+
+    def kernelMatrix(self, other: Optional["BatchedSimulator"] = None) -> np.ndarray:
+        """|overlapMatrix(other)|^2, float64: the fidelity kernel of the members.  Over a noisy
+        trajectory ensemble its mean is the purity Tr rho^2 of the average state."""
+        g = self.overlapMatrix(other)
+        return g.real * g.real + g.imag * g.imag
+
+    def overlapsWith(self, state) -> np.ndarray:
+        """<psi_t|s> for every member t, complex128 (B,) (qsim_batch_state_overlaps): one streaming
+        pass over the ensemble.  state: a StateVector, a Simulator, or a host array of 2^n
+        amplitudes (uploaded into a temporary StateVector)."""
+        tmp = None
+        if isinstance(state, Simulator):
+            state = state.state
+        elif not isinstance(state, StateVector):
+            tmp = StateVector(self._n)
+            tmp.fromHost(state)
+            state = tmp
+        out = np.empty(self._b, dtype=np.complex128)
+        try:
+            _lib.check(_lib.hip.qsim_batch_state_overlaps(self._h, state._h,
+                                                          out.ctypes.data_as(_c.POINTER(_c.c_double))))
+        finally:
+            if tmp is not None:
+                tmp.close()
+        return out
+
     def getAverageExpectation(self, observable) -> float:
         """Host mean of getExpectations, added in index order."""
         total = 0.0

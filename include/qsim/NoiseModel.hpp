@@ -165,6 +165,18 @@ public:
     // std::invalid_argument on a qubit-count mismatch.
     std::vector<double> getExpectations(const PauliSum& observable);
     double getAverageExpectation(const PauliSum& observable);
+    // Overlap matrices on the device (no reference counterpart; qsim_batch_overlaps): row-major
+    // G[i * B' + j] = <psi_i|phi_j> over this ensemble's trajectories and the other's (B' its batch
+    // size), or this ensemble's own Gram matrix — Hermitian bitwise, its diagonal's imaginary
+    // parts +0.  kernelMatrix is |G|^2 entry by entry (the fidelity kernel; its mean over a noisy
+    // ensemble is Tr rho^2).  overlapsWith: <psi_t|s> for every trajectory t
+    // (qsim_batch_state_overlaps).  Nothing is read back but the result, and the self case leaves
+    // the layout as it is.  std::invalid_argument on a qubit-count mismatch.
+    std::vector<std::complex<double>> overlapMatrix();
+    std::vector<std::complex<double>> overlapMatrix(BatchedSimulator& other);
+    std::vector<double> kernelMatrix();
+    std::vector<double> kernelMatrix(BatchedSimulator& other);
+    std::vector<std::complex<double>> overlapsWith(StateVector& state);
 
     int getNumQubits() const { return num_qubits_; }
     int getBatchSize() const { return batch_size_; }

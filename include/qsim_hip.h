@@ -586,6 +586,34 @@ int qsim_batch_histogram(qsim_batch* b, const double* uniforms, int shots, int64
 /* qsim_state_expectation on every trajectory: per_traj[t] = <psi_t|H|psi_t>, t < B (no reference
  * counterpart).  Carried Pauli frames are applied first; the qubit layout is left as it is. */
 int qsim_batch_expectation(qsim_batch* b, const qsim_pauli_term* terms, size_t count, double* per_traj);
+/* Overlap (Gram) matrices of ensembles, computed where the members lie (no reference counterpart).
+ * out: Ba x Bb complex, row-major, (re, im) interleaved: out[2 * (i * Bb + j)] = Re <a_i|b_j>.
+ * b == NULL or b == a: the self matrix G of a.  Only the upper triangle is computed; the lower one
+ * is written as its exact conjugate (G[j][i] == conj(G[i][j]) bitwise) and the diagonal's imaginary
+ * parts are +0.0.  Carried Pauli frames are applied first.  The self case reads the ensemble under
+ * whatever qsim_batch_perm the last run left (G does not depend on a relabeling that all members
+ * share): the layout is not restored and the amplitudes are not written.  The cross case reads in
+ * place when the two layouts are equal; otherwise both ensembles get the layout restore every
+ * index-based reader applies — the one case that moves data.
+ * The ensemble is a B x 2^n matrix and out = conj(A) B^T: tiles of 64 x 64 members times chunks of
+ * 2^n (qsim_batch_overlap_plan), each on v_mfma_f64_16x16x4_f64, its partial tile written to scratch;
+ * a second kernel adds an entry's partials in chunk order.  No floating-point atomics: the result is
+ * bitwise reproducible, and an entry depends on its two members alone.  QSIM_OVERLAP_MFMA=0 runs
+ * the same tiles with plain FMAs (cross-check).
+ * Null out, different qubit counts or different devices: QSIM_ERR_INVALID_ARGUMENT before any
+ * launch.  The scratch (a's) cannot be allocated: QSIM_ERR_DEVICE, nothing launched.  Synchronous. */
+int qsim_batch_overlaps(qsim_batch* a, qsim_batch* b, double* out);
+/* out: B complex, out[2 * t] = Re <a_t|s>: the call above with one column, always on the FMA kernel
+ * (a GEMV is memory-bound).  In place when the ensemble's and the state's layouts are equal, else
+ * both are restored.  The errors of the call above. */
+int qsim_batch_state_overlaps(qsim_batch* a, qsim_state* s, double* out);
+/* Host-only (no GPU): how the calls above cut their work up.  info[0] = path (0 FMA, 1 matrix
+ * core; 0 whenever batch_b == 1 or QSIM_OVERLAP_MFMA=0), [1] = row tiles, [2] = column tiles, [3] =
+ * tiles launched (self: the upper triangle only), [4] = K chunks, [5], [6] = partial-scratch bytes
+ * (chunks x tiles x 64 x 64 x 16), low and high word, [7] = 0.  Everything but [0] depends on the
+ * arguments alone.  self != 0 needs batch_a == batch_b.  Argument errors:
+ * QSIM_ERR_INVALID_ARGUMENT. */
+int qsim_batch_overlap_plan(int n_qubits, int batch_a, int batch_b, int self, int32_t info[8]);
 /* Current logical -> physical qubit map inside every trajectory, n entries (as qsim_state_perm). */
 int qsim_batch_perm(qsim_batch* b, int32_t* perm);
 int qsim_batch_device_ptr(qsim_batch* b, void** dptr);

@@ -258,10 +258,15 @@ bool plan_relayout(int n, const std::function<std::vector<Op>(const std::vector<
                    size_t max_passes, RelayoutChoice& out);
 // Up to QSIM_RELAYOUT_VARIANTS (default 3) closed tile sequences of the fewest passes, each with
 // QSIM_RELAYOUT_LAYOUT_VARIANTS (default 2) position choices: relayout choices, best predicted first — the candidates a timed first run compares; memoised.
-// period > 0 (run sharing): the circuit is copies of `period` gates each, and no pass holds a gate
-// more than one copy past its oldest gate's.
+// rule.period > 0 (run sharing): the circuit is `copies` copies of `period` gates each, and the
+// gates a pass may hoist from later copies are limited — cap_passes = 0: none more than one copy
+// past its oldest gate's; cap_passes = P > 0: by the pass's position in a plan aimed at P passes
+// (relayout.hip Search::copy_limit).
+struct ShareRule {
+    size_t period = 0, copies = 0, cap_passes = 0;
+};
 size_t plan_relayout_variants(int n, const std::function<std::vector<Op>(const std::vector<int>&)>& lower,
-                              size_t max_passes, std::vector<RelayoutChoice>& out, size_t period = 0);
+                              size_t max_passes, std::vector<RelayoutChoice>& out, const ShareRule& rule = {});
 bool relayout_enabled(int n);  // QSIM_RELAYOUT (default 1), QSIM_RELAYOUT_MIN_QUBITS (default 20)
 void relayout_configure(int mode, int min_qubits);  // qsim_set_relayout; < 0 leaves a setting
 // A single gate-free relayout pass taking logical qubit q from physical perm[q] to q (n >= 12).
@@ -277,6 +282,7 @@ bool relayout_forced();  // mode 2: a relayout plan whenever one exists (tests)
 struct SharePlan {
     int copies = 0;
     size_t count = 0;                        // gates per copy
+    size_t cap_passes = 0;                   // the position cap P the plan was searched under (0: the tail rule)
     std::vector<Op> ops;                     // the copies in order, lowered under layouts[0]
     Plan plan;
     std::vector<std::vector<int>> layouts;   // RelayoutChoice::layouts of the joint plan
@@ -293,7 +299,8 @@ bool share_advance(const SharePlan& sp, int& calls, size_t& next, size_t& first,
 // Requested gates (joint indices below calls * count) in passes >= next_pass, in circuit order.
 std::vector<int> share_pending(const SharePlan& sp, size_t next_pass, int calls);
 bool run_share_enabled(int n);  // QSIM_RUN_SHARE (default 1), from the relayout size threshold
-int run_share_copies();         // QSIM_RUN_SHARE_COPIES (default 4)
+// QSIM_RUN_SHARE_COPIES / qsim_set_run_share when set; else 4 below 26 qubits and 8 from there
+int run_share_copies(int n);
 void run_share_configure(int mode, int copies);  // qsim_set_run_share; negative: unchanged
 int tile_height_default();             // the h that hmax < 0 means (scope, setting, env, 6)
 int tile_height_for(int n);            // a single-GPU state's height (the setting, or by size)

@@ -29,6 +29,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <future>
 #include <mutex>
 #include <random>
 #include <unordered_set>
@@ -70,20 +71,26 @@ struct Search {
     // tile), and no pass could be launched before the last copy is requested; and with c + 1
     // allowed from the start, none before the second.  0: no limit.
     size_t period = 0, tail = 0;
-    // the first copy no gate of a pass over `rem` may come from
-    size_t copy_limit(const std::vector<int>& rem) const {
+    // The position cap (cap_passes = P > 0, instead of the rule above): the pass at position k
+    // of a joint plan of `copies` copies aimed at P passes may take gates of the copies below
+    // min(copies, k * copies / P + 1) — the copies requested by the time an evenly paced cycle
+    // reaches pass k — and always those of its oldest gate's copy, so every pass makes progress.
+    size_t copies = 0, cap_passes = 0;
+    // the first copy no gate of the pass at position `pos` over `rem` may come from
+    size_t copy_limit(const std::vector<int>& rem, size_t pos) const {
         if (period == 0) return SIZE_MAX;
         const size_t c = (size_t)rem[0] / period;
+        if (cap_passes > 0) return std::max(c + 1, std::min(copies, pos * copies / cap_passes + 1));
         const size_t left = std::lower_bound(rem.begin(), rem.end(), (int)((c + 1) * period)) - rem.begin();
         return left > tail ? c + 1 : c + 2;
     }
 
     // (gates admitted, gates partly covered) over the first `window` remaining gates
-    int score(const std::vector<int>& rem, uint64_t allowed) const {
+    int score(const std::vector<int>& rem, uint64_t allowed, size_t pos) const {
         uint64_t blocked = 0;
         int full = 0, part = 0;
         const size_t m = std::min(rem.size(), window);
-        const size_t lim = copy_limit(rem) * std::max<size_t>(period, 1);
+        const size_t lim = copy_limit(rem, pos) * std::max<size_t>(period, 1);
         for (size_t i = 0; i < m; ++i) {
             const uint64_t q = qm[rem[i]], nd = need[rem[i]];
             if ((q & blocked) || (period && (size_t)rem[i] >= lim)) {
@@ -97,12 +104,13 @@ struct Search {
         }
         return full * 4096 + part;
     }
-    // the gates a pass over `allowed` leaves (a gate runs unless it needs another qubit or shares
+    // the gates the pass at position `pos` over `allowed` leaves (a gate runs unless it needs another qubit or shares
     // one with a gate left behind: gates on disjoint qubits commute exactly)
-    std::vector<int> apply(const std::vector<int>& rem, uint64_t allowed, std::vector<int>* ran = nullptr) const {
+    std::vector<int> apply(const std::vector<int>& rem, uint64_t allowed, size_t pos,
+                           std::vector<int>* ran = nullptr) const {
         std::vector<int> out;
         uint64_t blocked = 0;
-        const size_t lim = rem.empty() ? 0 : copy_limit(rem) * std::max<size_t>(period, 1);
+        const size_t lim = rem.empty() ? 0 : copy_limit(rem, pos) * std::max<size_t>(period, 1);
         for (int i : rem) {
             const uint64_t q = qm[i];
             if ((q & blocked) == 0 && (need[i] & ~allowed) == 0 && !(period && (size_t)i >= lim)) {
@@ -167,7 +175,8 @@ std::vector<std::vector<uint64_t>> search_tiles(const Search& S, size_t nops, in
         for (const St& s : states) {
             const uint64_t prev = s.tiles.empty() ? 0ull : s.tiles.back();
             const uint64_t seed = S.need[s.rem.front()];
-            std::vector<std::pair<int, uint64_t>> part = {{S.score(s.rem, seed), seed}};
+            const size_t pos = s.tiles.size();
+            std::vector<std::pair<int, uint64_t>> part = {{S.score(s.rem, seed, pos), seed}};
             for (;;) {
                 bool grew = false;
                 std::vector<std::pair<int, uint64_t>> grown;
@@ -184,7 +193,7 @@ std::vector<std::vector<uint64_t>> search_tiles(const Search& S, size_t nops, in
                     const uint64_t cand = (sz + need < kTile ? all : prev) & ~h;
                     for (uint64_t m = cand; m; m &= m - 1) {
                         const uint64_t hh = h | (m & (~m + 1));
-                        if (dup.insert(hh).second) grown.push_back({S.score(s.rem, hh), hh});
+                        if (dup.insert(hh).second) grown.push_back({S.score(s.rem, hh, pos), hh});
                     }
                 }
                 if (!grew) break;
@@ -195,7 +204,7 @@ std::vector<std::vector<uint64_t>> search_tiles(const Search& S, size_t nops, in
             }
             for (const auto& pp : part) {
                 St t;
-                t.rem = S.apply(s.rem, pp.second);
+                t.rem = S.apply(s.rem, pp.second, pos);
                 // (finished sequences are all kept: they are the variants a timed first run compares)
                 if (t.rem.size() == s.rem.size() || (!t.rem.empty() && !seen.insert(t.rem).second)) continue;
                 t.tiles = s.tiles;
@@ -214,7 +223,7 @@ std::vector<std::vector<uint64_t>> search_tiles(const Search& S, size_t nops, in
             for (size_t i = 0; i < nops; ++i) rem[i] = (int)i;
             for (uint64_t t : s.tiles) {
                 std::vector<int> ran;
-                rem = S.apply(rem, t, &ran);
+                rem = S.apply(rem, t, U.size(), &ran);
                 uint64_t u = 0;
                 for (int i : ran) u |= S.need[i];
                 U.push_back(u);
@@ -369,7 +378,7 @@ bool build_choice(int n, const std::function<std::vector<Op>(const std::vector<i
     {
         std::vector<int> rem(logical.size());
         for (size_t i = 0; i < rem.size(); ++i) rem[i] = (int)i;
-        for (size_t k = 0; k < K; ++k) rem = S.apply(rem, T[k], &ran[k]);
+        for (size_t k = 0; k < K; ++k) rem = S.apply(rem, T[k], k, &ran[k]);
         if (!rem.empty()) return false;
     }
     // runs: R[k] (loaded by pass k) from T[k-1] & T[k], R[0] from T[K-1] & T[0]
@@ -474,10 +483,34 @@ std::vector<unsigned char> ops_key(const std::vector<Op>& ops) {
     }
     return k;
 }
+// Every gate's qubits and the ones a tile must hold; false when a gate leaves no room for a run.
+bool gate_masks(const std::vector<Op>& logical, std::vector<uint64_t>& qm, std::vector<uint64_t>& nd) {
+    qm.resize(logical.size());
+    nd.resize(logical.size());
+    bool fits = true;
+    for (size_t i = 0; i < logical.size(); ++i) {
+        qm[i] = op_mask(logical[i]);
+        nd[i] = op_need(logical[i], tile_ctrl_out());
+        fits = fits && __builtin_popcountll(nd[i]) <= kTile - kRun;
+    }
+    return fits;
+}
+Search make_search(const std::vector<uint64_t>& qm, int n, const std::vector<uint64_t>& nd, const ShareRule& rule) {
+    Search S{qm, n, nd};
+    S.period = rule.period;
+    S.tail = rule.period * (size_t)share_tail_percent() / 100;
+    S.copies = rule.copies;
+    S.cap_passes = rule.cap_passes;
+    return S;
+}
+int beam_width(size_t nops) {
+    static const int width = env_int("QSIM_RELAYOUT_BEAM", 96);
+    return std::max(2, (int)(width * 256.0 / std::max<size_t>(256, nops)));
+}
 }  // namespace
 
 size_t plan_relayout_variants(int n, const std::function<std::vector<Op>(const std::vector<int>&)>& lower,
-                              size_t max_passes, std::vector<RelayoutChoice>& out, size_t period) {
+                              size_t max_passes, std::vector<RelayoutChoice>& out, const ShareRule& rule) {
     out.clear();
     if (n < kTile + kRun || n - kTile > 32) return 0;
     std::vector<int> id(n);
@@ -485,7 +518,8 @@ size_t plan_relayout_variants(int n, const std::function<std::vector<Op>(const s
     const std::vector<Op> logical = lower(id);
     if (logical.empty()) return 0;
     std::vector<unsigned char> key = ops_key(logical);
-    for (int b = 0; b < 8; ++b) key.push_back((unsigned char)(period >> (8 * b)));
+    for (size_t v : {rule.period, rule.copies, rule.cap_passes})
+        for (int b = 0; b < 8; ++b) key.push_back((unsigned char)(v >> (8 * b)));
     {
         std::lock_guard<std::mutex> l(g_rl_mu);
         for (RelayoutMemo& m : g_rl_memo)
@@ -495,21 +529,12 @@ size_t plan_relayout_variants(int n, const std::function<std::vector<Op>(const s
                 return out.size();
             }
     }
-    std::vector<uint64_t> qm(logical.size()), nd(logical.size());
-    bool fits = true;
-    for (size_t i = 0; i < logical.size(); ++i) {
-        qm[i] = op_mask(logical[i]);
-        nd[i] = op_need(logical[i], tile_ctrl_out());
-        fits = fits && __builtin_popcountll(nd[i]) <= kTile - kRun;
-    }
-    if (fits) {
-        Search S{qm, n, nd};
-        S.period = period;
-        S.tail = period * (size_t)share_tail_percent() / 100;
-        static const int width = env_int("QSIM_RELAYOUT_BEAM", 96);
+    std::vector<uint64_t> qm, nd;
+    if (gate_masks(logical, qm, nd)) {
+        const Search S = make_search(qm, n, nd, rule);
         static const int nvar = std::max(1, env_int("QSIM_RELAYOUT_VARIANTS", 3));
         static const int nlay = std::max(1, env_int("QSIM_RELAYOUT_LAYOUT_VARIANTS", 2));
-        const int w = std::max(2, (int)(width * 256.0 / std::max<size_t>(256, logical.size())));
+        const int w = beam_width(logical.size());
         for (const std::vector<uint64_t>& T : search_tiles(S, logical.size(), w, std::min<size_t>(max_passes, 64), nvar)) {
             for (int ls = 0; ls < nlay; ++ls) {  // layout variants of the sequence (unique first layouts:
                                                  // a memoised choice is found again by it)
@@ -584,23 +609,28 @@ Plan plan_permutation_pass(int n, const std::vector<int>& from, const std::vecto
 // ---------------------------------------------------------------------------------------
 // Run sharing: the joint plan of `copies` runs of one circuit and its piecewise bookkeeping.
 // ---------------------------------------------------------------------------------------
-static std::atomic<int> g_share{-1}, g_share_copies{-1};
+static std::atomic<int> g_share{-1}, g_share_copies{-1};  // copies 0: not set (by state size)
+static int clamp_copies(int c) { return c <= 0 ? 0 : std::min(16, std::max(2, c)); }
 static void share_defaults() {
     if (g_share.load() < 0) g_share.store(env_int("QSIM_RUN_SHARE", 1) != 0 ? 1 : 0);
-    if (g_share_copies.load() < 0) g_share_copies.store(std::min(16, std::max(2, env_int("QSIM_RUN_SHARE_COPIES", 4))));
+    if (g_share_copies.load() < 0) g_share_copies.store(clamp_copies(env_int("QSIM_RUN_SHARE_COPIES", 0)));
 }
 bool run_share_enabled(int n) {
     share_defaults();
     return g_share.load() != 0 && relayout_enabled(n);
 }
-int run_share_copies() {
+// Unset: 4 copies below 26 qubits (the calibration threshold) and 8 from there, where a pass takes
+// milliseconds and the longer cycle's arming (joint planning, about twice the kernels to compile)
+// is paid back by calls that launch two passes instead of three.
+int run_share_copies(int n) {
     share_defaults();
-    return g_share_copies.load();
+    const int c = g_share_copies.load();
+    return c > 0 ? c : n >= 26 ? 8 : 4;
 }
 void run_share_configure(int mode, int copies) {
     share_defaults();
     if (mode >= 0) g_share.store(mode != 0 ? 1 : 0);
-    if (copies >= 0) g_share_copies.store(std::min(16, std::max(2, copies)));
+    if (copies >= 0) g_share_copies.store(clamp_copies(copies));
 }
 
 // QSIM_RUN_SHARE_TAIL (per cent, default 50; include/qsim_hip.h qsim_set_run_share): the share of
@@ -610,12 +640,63 @@ static int share_tail_percent() {
     return v;
 }
 
+namespace {
+// The largest number of passes one of the calls 1 .. copies - 1 of a cycle launches (share_advance
+// on the passes' highest copies): the last call's count is what is left and not a choice.
+int share_max_call(const std::vector<int>& pass_copy, int copies) {
+    int worst = 0;
+    size_t k = 0;
+    for (int call = 1; call < copies; ++call) {
+        const size_t first = k;
+        while (k < pass_copy.size() && pass_copy[k] < call) ++k;
+        worst = std::max(worst, (int)(k - first));
+    }
+    return worst;
+}
+std::vector<int> share_pass_copy(const std::vector<std::vector<int>>& pass_src, size_t count) {
+    std::vector<int> out;
+    for (const std::vector<int>& src : pass_src) {
+        int c = -1;
+        for (int g : src) c = std::max(c, (int)((size_t)g / count));
+        out.push_back(c);
+    }
+    return out;
+}
+// The fewest-pass closed tile sequence under `rule`, without layouts or kernels: its pass count
+// and share_max_call (0 passes: none found).  Touches no shared state: plan_share runs the
+// position caps of a sweep side by side.
+struct ShareProbe {
+    size_t cap_passes = 0, joint = 0;
+    int max_call = 0;
+};
+ShareProbe probe_share(const std::vector<uint64_t>& qm, int n, const std::vector<uint64_t>& nd, const ShareRule& rule,
+                       int width) {
+    ShareProbe out;
+    out.cap_passes = rule.cap_passes;
+    const Search S = make_search(qm, n, nd, rule);
+    const std::vector<std::vector<uint64_t>> seqs = search_tiles(S, qm.size(), width, 64, 1);
+    if (seqs.empty()) return out;
+    std::vector<std::vector<int>> ran(seqs[0].size());
+    std::vector<int> rem(qm.size());
+    for (size_t i = 0; i < rem.size(); ++i) rem[i] = (int)i;
+    for (size_t k = 0; k < ran.size(); ++k) rem = S.apply(rem, seqs[0][k], k, &ran[k]);
+    if (!rem.empty()) return out;
+    out.joint = ran.size();
+    out.max_call = share_max_call(share_pass_copy(ran, rule.period), (int)rule.copies);
+    return out;
+}
+// The memo's rule identity: bump when the planner's choice for one key may change.
+constexpr int64_t kShareRuleId = 2;  // 2: the better of the tail rule and a sweep of position caps
+}  // namespace
+
 bool plan_share(int n, const qsim_gate* gates, size_t count, int copies, size_t single_passes, SharePlan& out) {
     if (copies < 2 || count == 0 || single_passes == 0) return false;
     const TileHeightScope scope(6, tile_rb_for(n, 6));
     // memo key (kind 4: never read as a single-run decision): everything the answer depends on —
     // the gates' meaningful fields (no padding, no unused qubit slots), the number of copies, the
-    // single plan's pass count the joint plan is compared with, and the hoisting limit
+    // single plan's pass count the joint plan is compared with, the hoisting limit and the rule
+    // identity (an entry of a planner that knew one rule only is never read as this one's).  The
+    // entry holds the chosen position cap P (0: the tail rule) in front of the first layout.
     std::vector<unsigned char> key;
     auto put = [&](const void* p, size_t b) {
         const unsigned char* c = static_cast<const unsigned char*>(p);
@@ -628,46 +709,134 @@ bool plan_share(int n, const qsim_gate* gates, size_t count, int copies, size_t 
         put(f, sizeof f);
         put(&gates[i].parameter, sizeof(double));
     }
-    const int64_t tailkey[3] = {copies, (int64_t)single_passes, share_tail_percent()};
+    const int64_t tailkey[4] = {copies, (int64_t)single_passes, share_tail_percent(), kShareRuleId};
     put(tailkey, sizeof tailkey);
     std::vector<int> memo;
     const bool have_memo = layout_memo_get(n, 4, key.data(), key.size(), memo);
     if (have_memo && memo.empty()) return false;  // decided before: no cycle pays for this circuit
-    const size_t total = count * (size_t)copies;
-    auto lower = [&](const std::vector<int>& pi) {  // the copies in order, as runSequence lowers them
-        std::vector<Op> ops;
-        ops.reserve(total);
-        for (size_t i = 0; i < total; ++i) {
-            qsim_gate g = gates[i % count];
-            for (int j = 0; j < g.nqubits && j < 3; ++j) g.qubits[j] = pi[g.qubits[j]];
-            ops.push_back(lower_gate(g, n));
-            ops.back().src = (int)i;
+    auto lower_copies = [&](size_t total) {  // the copies in order, as runSequence lowers them
+        return [&, total](const std::vector<int>& pi) {
+            std::vector<Op> ops;
+            ops.reserve(total);
+            for (size_t i = 0; i < total; ++i) {
+                qsim_gate g = gates[i % count];
+                for (int j = 0; j < g.nqubits && j < 3; ++j) g.qubits[j] = pi[g.qubits[j]];
+                ops.push_back(lower_gate(g, n));
+                ops.back().src = (int)i;
+            }
+            return ops;
+        };
+    };
+    const auto lower = lower_copies(count * (size_t)copies);
+    // The variant of one rule to keep: the fewest passes, then the smallest largest call, then the
+    // predicted cost (the variants come sorted by passes, then cost); the memoised one if present.
+    auto pick = [&](std::vector<RelayoutChoice>& vs, const std::vector<int>* perm) {
+        RelayoutChoice* rc = nullptr;
+        int best = 0;
+        for (RelayoutChoice& v : vs) {
+            if (perm) {
+                if (v.perm == *perm) return &v;
+                continue;
+            }
+            if (v.plan.passes.size() != vs.front().plan.passes.size()) break;
+            const int mc = share_max_call(share_pass_copy(v.pass_src, count), copies);
+            if (!rc || mc < best) {
+                rc = &v;
+                best = mc;
+            }
         }
-        return ops;
+        return rc;
     };
     std::vector<RelayoutChoice> vs;
-    plan_relayout_variants(n, lower, SIZE_MAX, vs, count);
     RelayoutChoice* rc = nullptr;
-    for (RelayoutChoice& v : vs)
-        if (have_memo && v.perm == memo) rc = &v;
-    if (!rc && !vs.empty()) rc = &vs.front();  // the best predicted variant
-    if (!rc || rc->plan.passes.size() >= (size_t)copies * single_passes) {
-        if (!have_memo) layout_memo_put(n, 4, key.data(), key.size(), {});
-        return false;
+    size_t cap = 0;
+    if (have_memo) {
+        cap = (size_t)memo.front();
+        const std::vector<int> perm(memo.begin() + 1, memo.end());
+        plan_relayout_variants(n, lower, SIZE_MAX, vs, ShareRule{count, (size_t)copies, cap});
+        rc = pick(vs, &perm);
+        if (!rc) rc = pick(vs, nullptr);
+        if (!rc) return false;
+    } else {
+        // the tail rule's plan first: a candidate, and its pass count ends the sweep
+        cap = 0;
+        plan_relayout_variants(n, lower, SIZE_MAX, vs, ShareRule{count, (size_t)copies, 0});
+        rc = pick(vs, nullptr);
+        // (whether a cycle pays at all stays the tail rule's decision: no sweep for a refused circuit)
+        const size_t limit = (size_t)copies * single_passes;
+        if (!rc || rc->plan.passes.size() >= limit) {
+            layout_memo_put(n, 4, key.data(), key.size(), {});
+            return false;
+        }
+        const size_t today = rc->plan.passes.size();
+        const int today_call = share_max_call(share_pass_copy(rc->pass_src, count), copies);
+        // position caps P = copies * (one copy's passes) / 2 .. today's count, probed on tile sequences only and
+        // side by side (each is one beam search, seconds at 30 qubits): the order below decides, so
+        // the choice does not depend on how many ran at once
+        std::vector<int> id(n);
+        for (int q = 0; q < n; ++q) id[q] = q;
+        const std::vector<Op> logical = lower(id);
+        std::vector<uint64_t> qm, nd;
+        std::vector<ShareProbe> probes;
+        if (gate_masks(logical, qm, nd)) {
+            // (one copy's passes as a relayout plan of its own: the circuit's, not those of the plan
+            // the caller happened to run, so a state and the host view sweep the same caps)
+            RelayoutChoice alone;
+            const size_t single = plan_relayout(n, lower_copies(count), SIZE_MAX, alone) ? alone.plan.passes.size()
+                                                                                       : single_passes;
+            const size_t lo = std::max<size_t>(2, (size_t)copies * single / 2), hi = std::min<size_t>(today, 63);
+            (void)share_tail_percent();  // (read once here, not first by a probe thread)
+            const int width = beam_width(logical.size());
+            if (lo <= hi) probes.resize(hi - lo + 1);
+            std::atomic<size_t> next_probe{0};
+            auto work = [&] {
+                for (size_t i; (i = next_probe.fetch_add(1)) < probes.size();)
+                    probes[i] = probe_share(qm, n, nd, ShareRule{count, (size_t)copies, lo + i}, width);
+            };
+            std::vector<std::future<void>> threads;
+            for (size_t t = 1; t < std::min<size_t>(probes.size(), 8); ++t)
+                threads.push_back(std::async(std::launch::async, work));
+            work();
+            for (std::future<void>& f : threads) f.get();
+        }
+        probes.erase(std::remove_if(probes.begin(), probes.end(),
+                                    [&](const ShareProbe& p) {
+                                        return p.joint == 0 || p.joint > today ||
+                                               (p.joint == today && p.max_call >= today_call);
+                                    }),
+                     probes.end());
+        std::stable_sort(probes.begin(), probes.end(), [](const ShareProbe& x, const ShareProbe& y) {
+            return x.joint != y.joint ? x.joint < y.joint : x.max_call < y.max_call;
+        });
+        // the best probe whose layouts can be built and whose plan is what the probe promised
+        for (const ShareProbe& p : probes) {
+            std::vector<RelayoutChoice> cs;
+            plan_relayout_variants(n, lower, SIZE_MAX, cs, ShareRule{count, (size_t)copies, p.cap_passes});
+            RelayoutChoice* c = pick(cs, nullptr);
+            if (!c || c->plan.passes.size() > p.joint ||
+                share_max_call(share_pass_copy(c->pass_src, count), copies) > p.max_call)
+                continue;
+            vs = std::move(cs);
+            rc = pick(vs, nullptr);
+            cap = p.cap_passes;
+            break;
+        }
+        if (std::getenv("QSIM_RELAYOUT_DEBUG"))
+            std::fprintf(stderr, "[share] %d copies: tail rule %zu passes (largest call %d), kept cap P = %zu: %zu passes\n",
+                         copies, today, today_call, cap, rc->plan.passes.size());
+        std::vector<int> entry = {(int)cap};
+        entry.insert(entry.end(), rc->perm.begin(), rc->perm.end());
+        layout_memo_put(n, 4, key.data(), key.size(), entry);
     }
-    if (!have_memo) layout_memo_put(n, 4, key.data(), key.size(), rc->perm);
+    if (rc->plan.passes.size() >= (size_t)copies * single_passes) return false;
     out.copies = copies;
     out.count = count;
+    out.cap_passes = cap;
     out.ops = std::move(rc->ops);
     out.plan = std::move(rc->plan);
     out.layouts = std::move(rc->layouts);
     out.pass_src = std::move(rc->pass_src);
-    out.pass_copy.clear();
-    for (const std::vector<int>& src : out.pass_src) {
-        int c = -1;
-        for (int g : src) c = std::max(c, (int)((size_t)g / count));
-        out.pass_copy.push_back(c);
-    }
+    out.pass_copy = share_pass_copy(out.pass_src, count);
     return true;
 }
 
@@ -940,7 +1109,7 @@ extern "C" int qsim_plan_share_host(int n_qubits, const qsim_gate* gates, size_t
         if (!amps || !gates || count == 0 || calls < 0) fail(QSIM_ERR_INVALID_ARGUMENT, "bad argument");
         const int n = n_qubits;
         for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n);
-        if (copies <= 0) copies = run_share_copies();
+        if (copies <= 0) copies = run_share_copies(n_qubits);
         std::vector<int> cur;
         Plan single;
         host_single_plan(n, gates, count, cur, single);
@@ -1011,7 +1180,7 @@ extern "C" int qsim_plan_share_info(int n_qubits, const qsim_gate* gates, size_t
         if (n_qubits < 10 || n_qubits > 40) fail(QSIM_ERR_INVALID_ARGUMENT, "bad qubit count");
         if (!gates || count == 0) fail(QSIM_ERR_INVALID_ARGUMENT, "bad argument");
         for (size_t i = 0; i < count; ++i) validate_gate(gates[i], n_qubits);
-        if (copies <= 0) copies = run_share_copies();
+        if (copies <= 0) copies = run_share_copies(n_qubits);
         std::vector<int> perm;
         Plan single;
         host_single_plan(n_qubits, gates, count, perm, single);
@@ -1024,8 +1193,8 @@ extern "C" int qsim_plan_share_info(int n_qubits, const qsim_gate* gates, size_t
 }
 
 extern "C" int qsim_set_run_share(int mode, int copies) {
-    if (mode > 1 || (copies >= 0 && copies < 2)) {
-        qsim_hip::set_last_error("run share: mode 0 or 1, at least 2 copies");
+    if (mode > 1 || copies == 1) {
+        qsim_hip::set_last_error("run share: mode 0 or 1, at least 2 copies (0: by state size)");
         return QSIM_ERR_INVALID_ARGUMENT;
     }
     qsim_hip::run_share_configure(mode, copies);

@@ -116,7 +116,7 @@ static void share_arm_impl(qsim_state* s, const qsim_gate* gates, size_t count) 
     const int n = s->n;
     if (s->pinned || s->share_block || !run_share_enabled(n) || !relabel_mode_on() || tile_height_is_set()) return;
     if (!s->share) s->share = std::make_unique<ShareState>();
-    const int copies = run_share_copies();
+    const int copies = run_share_copies(n);
     if (!(s->share->have || s->share->refused) || !same_gates(s->share->gates, gates, count) ||
         (s->share->have && s->share->sp.copies != copies)) {
         if (s->share->jit.mod) QSIM_HIPCHK(hipStreamSynchronize(s->stream));  // its kernels may be queued

@@ -156,7 +156,8 @@ def set_relayout(mode: int = -1, min_qubits: int = -1) -> None:
 
 def set_run_share(mode: int = -1, copies: int = -1) -> None:
     """Run sharing (qsim_set_run_share): repeated fused runs of one circuit executed as calls of
-    ONE joint relayout plan of `copies` runs (default 4); gates a call could not yet run stay
+    ONE joint relayout plan of `copies` runs (0, the default: 4 below 26 qubits, 8 from there); gates
+    a call could not yet run stay
     pending until the next call or the next reader of the state.  mode 0 off, 1 on (default, for
     states from the relayout size threshold); negative arguments leave a setting unchanged."""
     _lib.check(_lib.hip.qsim_set_run_share(mode, copies))
@@ -188,13 +189,13 @@ def set_tile_ctrl_out(mode: int = -1) -> None:
 
 # The shipped policy (include/qsim_hip.h; environment variables unset).
 DEFAULTS = {"jit": (1, 20), "relabel": (1, 26), "relayout": (1, 20), "calibrate": (1, 26),
-            "run_share": (1, 4)}
+            "run_share": (1, 0)}
 
 
 def restore_defaults() -> None:
     """Put every process-wide planning policy back to the shipped defaults: background JIT from
     20 qubits, relabeling from 26, relayout plans from 20, calibrated first runs from 26 (with
-    inline compilation), run sharing on with 4 copies, the size rule for tile heights (tests call this after changing any)."""
+    inline compilation), run sharing on with its cycle length by state size, the size rule for tile heights (tests call this after changing any)."""
     set_jit(*DEFAULTS["jit"])
     set_relabel(*DEFAULTS["relabel"])
     set_relayout(*DEFAULTS["relayout"])

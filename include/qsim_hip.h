@@ -247,8 +247,14 @@ int qsim_plan_relayout(int n_qubits, const qsim_gate* gates, size_t count, int32
  * 2^k - 1 (at most 63) identical repeats run unshared before it arms again.  A failure while
  * arming (planning, compile, launch) leaves the run that triggered it successful and unshared.
  * mode 0 off (every run executes its own plan, as before), 1 on (default, QSIM_RUN_SHARE) for
- * states from the relayout size threshold; copies >= 2 (default 4, QSIM_RUN_SHARE_COPIES);
- * negative arguments leave a setting unchanged.  QSIM_RUN_SHARE_TAIL (per cent, default 50, read
+ * states from the relayout size threshold; copies >= 2 (QSIM_RUN_SHARE_COPIES), or 0 (default):
+ * 4 below 26 qubits and 8 from there, where a pass takes milliseconds and the longer cycle's
+ * arming (joint planning: seconds at 30 qubits; about 21 kernels to compile instead of 12) pays
+ * off; negative arguments leave a setting unchanged.  The joint plan is the better of the tail
+ * rule's (below) and a sweep of position caps (the pass at position k of a plan aimed at P passes
+ * takes gates of the copies below min(copies, k * copies / P + 1)): the fewest passes, then the
+ * smallest largest call before the last.  The last call of a cycle launches what is left, up to
+ * about twice a single run's passes.  QSIM_RUN_SHARE_TAIL (per cent, default 50, read
  * once): the share of a copy's gates that must have run before a joint pass may also take gates
  * of the next copy (100: from the start; fewer passes, but the first call of a cycle launches
  * none). */
